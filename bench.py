@@ -18,6 +18,15 @@ shared top fronts distributed by column slabs (owner-computes), each 512-column 
 column summed with a reduce-scatter by row chunks before its panel chain and gathered
 after it -- the engine calls RCCL itself; strong scaling.
 `--gpus N` without a launcher around it starts the N ranks itself.
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline
+figure and what the timed run itself reports.  Everything else the bench measures
+or checks -- the same step through the public API, the profiled pass and its
+roofline, the solve with its residual and factor invariants, the CPU baseline, the
+secondary workloads and the micro-benchmarks of the update kernel and the MFMA
+ceiling -- runs under `--full` (the `--no-*` options pick among them there).
+`--dump-outputs DIR` writes, after the timed steps, what the factor of the last
+timed step gives its caller (dump_outputs below) as .npy files.
 """
 from __future__ import annotations
 
@@ -562,6 +571,38 @@ def complex_line(m=64, steps=3):
     return out
 
 
+DUMP_SAMPLE = 1 << 20       # entries of the solution --dump-outputs writes at most (8 MiB of float64)
+
+
+def dump_outputs(S, Lf, n, out_dir, rank, world):
+    """--dump-outputs DIR: what the factor of the last timed step gives its caller, so that two builds can be compared
+    output for output.  The factor stays in HBM (181.6 GB at 200^3); it is read the way a caller reads it, right after the
+    timed steps and before anything factorizes again:
+      solution.npy           x = A \\ b through cholmod_l_solve on that factor, b = the demo right-hand side (demo_rhs):
+                             all n entries up to DUMP_SAMPLE, above that the entries at DUMP_SAMPLE indices drawn once with
+                             a fixed seed, in increasing order
+      factor_invariants.npy  one pass over the factor on the device (cholmod_hip_factor_checks): sum_j log L(j,j), nonzeros
+                             in the dead upper triangles of the diagonal blocks, non-finite entries, ||L||_F^2, diagonal
+                             entries <= 0
+    float64, at most 8.4 MB in all.  Several ranks: every rank gathers the factor, rank 0 writes."""
+    from suitesparse_amd import cholmod as ch
+    from suitesparse_amd import generators as G
+    if world > 1 and S.L.cholmod_l_gather_factor(Lf, C.byref(S.cm)) != 1:
+        raise RuntimeError(f"--dump-outputs: the factor cannot be gathered on rank {rank} (status {S.cm.status})")
+    if rank != 0:
+        return
+    chk = S.factor_checks(Lf)
+    x = S.solve(Lf, G.demo_rhs(n))
+    assert S.cm.status == ch.OK, S.cm.status
+    if n > DUMP_SAMPLE:
+        x = x[np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "solution.npy"), np.ascontiguousarray(x, dtype=np.float64))
+    np.save(os.path.join(out_dir, "factor_invariants.npy"),
+            np.array([chk[k] for k in ("half_logdet", "upper_nonzeros", "nonfinite", "fro2", "nonpositive_diag")],
+                     dtype=np.float64))
+
+
 def visible_devices():
     """HIP devices this process can see (the engine's own probe: no torch, no device context)."""
     from suitesparse_amd import cholmod as ch
@@ -870,6 +911,11 @@ def main():
     ap.add_argument("--workload", default="poisson3d")
     ap.add_argument("--grid", "--m", dest="m", type=int, default=0,
                     help="grid points per side (default: 200, falling back to 160 / 100 if HBM is short)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the API step, the profiled pass (roofline), the solve and factor "
+                         "checks, the CPU baseline, the secondary workloads and the kernel micro-benchmarks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the factor of the last timed step gives its caller to DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-sample-m", type=int, default=100,
                     help="CPU baseline: Poisson m^3 through the product's CPU path (default 100 = BASELINE configs[1])")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -877,9 +923,9 @@ def main():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the other single-GPU configurations (Poisson 100^3, the nd24k and G3_circuit stand-ins) "
                          "that follow the headline workload in the same JSON line")
-    ap.add_argument("--check", action="store_true", help="(default; kept for old command lines)")
+    ap.add_argument("--check", action="store_true", help="(default under --full; kept for old command lines)")
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the solve / residual / factor invariants after the timed region")
+                    help="skip the solve / residual / factor invariants after the timed region (--full)")
     ap.add_argument("--hip-flags", type=int, default=0)
     ap.add_argument("--matrix", default=None,
                     help="factor a symmetric positive definite Matrix Market / triplet file instead of a synthetic "
@@ -1090,28 +1136,35 @@ def main():
     stats = S.hip_stats(Lf)
     exec_flops = stats[1]
 
-    # the same step through the public API (SURVEY 8d's t_factorize): cholmod_l_factorize
-    # from the host matrix.  The first call permutes A into S = tril(PAP') on the host cores
-    # and uploads S; calls with the same pattern (these) send A->x only and gather it into
-    # the resident S on the device; L stays in HBM
-    # (one untimed call first: the pinned staging buffer of the value upload is allocated by the first call of this kind;
-    # a short step is repeated until the loop lasts a quarter of a second)
-    assert S.factorize(A, Lf) == 1 and S.cm.status == ch.OK
-    api_steps = max(min(args.steps, 3), min(50, int(0.25 * args.steps / max(elapsed, 1e-6))))
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(api_steps):
+    if args.dump_outputs:
+        wd.arm("writing the outputs of the last timed step (--dump-outputs)", None)
+        dump_outputs(S, Lf, n, args.dump_outputs, rank, world)
+        wd.arm("after the timed region (API steps, profiled pass, checks, secondary workloads)", None)
+
+    if args.full:
+        # the same step through the public API (SURVEY 8d's t_factorize): cholmod_l_factorize
+        # from the host matrix.  The first call permutes A into S = tril(PAP') on the host cores
+        # and uploads S; calls with the same pattern (these) send A->x only and gather it into
+        # the resident S on the device; L stays in HBM
+        # (one untimed call first: the pinned staging buffer of the value upload is allocated by the first call of this kind;
+        # a short step is repeated until the loop lasts a quarter of a second)
         assert S.factorize(A, Lf) == 1 and S.cm.status == ch.OK
-    barrier()
-    elapsed_api = time.perf_counter() - t0
-    if dist is not None:
-        import torch
-        t = torch.tensor([elapsed_api], device="cuda", dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed_api = float(t.item())
+        api_steps = max(min(args.steps, 3), min(50, int(0.25 * args.steps / max(elapsed, 1e-6))))
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(api_steps):
+            assert S.factorize(A, Lf) == 1 and S.cm.status == ch.OK
+        barrier()
+        elapsed_api = time.perf_counter() - t0
+        if dist is not None:
+            import torch
+            t = torch.tensor([elapsed_api], device="cuda", dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed_api = float(t.item())
 
     roof = None
-    if not args.no_profile_pass:
+    profile_pass = args.full and not args.no_profile_pass
+    if profile_pass:
         roof = roofline_of(S, Lf, wname, world)
 
     # correctness of what was just timed (outside the timed region): device solve ->
@@ -1119,9 +1172,9 @@ def main():
     # Poisson grids log det(A) is known in closed form (a checksum of the whole factor)
     resid, checks = None, None
     check_note = None
-    do_check = not args.no_check
+    do_check = args.full and not args.no_check
     dist_checks = None
-    if not args.no_check and world > 1:
+    if do_check and world > 1:
         # invariants of the factor as it lies distributed over the ranks (every front checked by the first rank
         # of its group, the five sums all-reduced): no gathered copy, so this works where the gather does not fit
         import torch
@@ -1182,11 +1235,12 @@ def main():
     S.finish()
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_sample_m)
         # the other single-GPU configurations of BASELINE.json, in the same record (a few seconds each)
         secondary = []
-        if world == 1 and not args.no_secondary and not args.matrix and args.workload == "poisson3d" and m >= 160:
+        if (args.full and world == 1 and not args.no_secondary and not args.matrix and args.workload == "poisson3d"
+                and m >= 160):
             # (box3d 50: the nd24k stand-in's stencil on a grid whose factorization has the flop count SURVEY 8d records for the
             # 42^3 stand-in under AMD, 2.4e12 -- under this build's nested dissection 42^3 itself is 8.0e11, a third of it)
             for wl, mm in (("poisson3d", 100), ("box3d", 42), ("poisson2d", 1259), ("box3d", 50)):
@@ -1198,26 +1252,27 @@ def main():
                 secondary.append(complex_line(64))
             except Exception as e:
                 secondary.append({"workload": "hermitian_poisson3d_64", "error": repr(e)})
-        pr = ch.probes()            # micro-benchmarks: lib/libcholmod_amd_probes.so, not the product library
-        mf = pr.cholmod_hip_bench_update_kernel(8192, 8192, 512, 3, 8192)
-        mf_big = pr.cholmod_hip_bench_update_kernel(16384, 16384, 4096, 2, 8192)
-        mf2_big = pr.cholmod_hip_bench_update_kernel(16384, 16384, 4096, 2, 0)
-        # The fp64 matrix-core ceiling, measured: an inline-assembly v_mfma_f64_16x16x4 loop with
-        # nothing else in it, ~0.25 s per point so that the clock settles (waves per SIMD x
-        # accumulators x operand data: full-mantissa operands cost power, i.e. clock).  Issue
-        # rate = 64 cycles per MFMA per SIMD exactly, so the ceiling is 78.6 TFLOP/s x clock / 2.4 GHz.
-        import ctypes as C2
-        sweep = {}
-        for zero in (0, 1):
-            for nacc in (4, 8):
-                for w in (1, 2):
-                    o3 = (C2.c_double * 3)()
-                    r = pr.cholmod_hip_bench_mfma_ceiling(w, nacc, int(0.25 * 2.3e9 / (4 * nacc * 64 * w)), zero, o3)
-                    if r > 0:
-                        sweep[f"{'zero' if zero else 'data'}_acc{nacc}_waves{w}"] = {
-                            "TFLOPs": r / 1e12, "clock_GHz": o3[1], "cycles_per_mfma_per_simd": o3[0] if w == 1 else None}
-        data_pts = [v["TFLOPs"] for k, v in sweep.items() if k.startswith("data")]
-        mpeak = max(data_pts) * 1e12 if data_pts else 0.0
+        if args.full:
+            pr = ch.probes()            # micro-benchmarks: lib/libcholmod_amd_probes.so, not the product library
+            mf = pr.cholmod_hip_bench_update_kernel(8192, 8192, 512, 3, 8192)
+            mf_big = pr.cholmod_hip_bench_update_kernel(16384, 16384, 4096, 2, 8192)
+            mf2_big = pr.cholmod_hip_bench_update_kernel(16384, 16384, 4096, 2, 0)
+            # The fp64 matrix-core ceiling, measured: an inline-assembly v_mfma_f64_16x16x4 loop with
+            # nothing else in it, ~0.25 s per point so that the clock settles (waves per SIMD x
+            # accumulators x operand data: full-mantissa operands cost power, i.e. clock).  Issue
+            # rate = 64 cycles per MFMA per SIMD exactly, so the ceiling is 78.6 TFLOP/s x clock / 2.4 GHz.
+            import ctypes as C2
+            sweep = {}
+            for zero in (0, 1):
+                for nacc in (4, 8):
+                    for w in (1, 2):
+                        o3 = (C2.c_double * 3)()
+                        r = pr.cholmod_hip_bench_mfma_ceiling(w, nacc, int(0.25 * 2.3e9 / (4 * nacc * 64 * w)), zero, o3)
+                        if r > 0:
+                            sweep[f"{'zero' if zero else 'data'}_acc{nacc}_waves{w}"] = {
+                                "TFLOPs": r / 1e12, "clock_GHz": o3[1], "cycles_per_mfma_per_simd": o3[0] if w == 1 else None}
+            data_pts = [v["TFLOPs"] for k, v in sweep.items() if k.startswith("data")]
+            mpeak = max(data_pts) * 1e12 if data_pts else 0.0
         value = fl * args.steps / elapsed / 1e9        # one job, all ranks together
         line = {
             "metric": METRIC,
@@ -1236,30 +1291,33 @@ def main():
                        "input": "S=tril(PAP') resident in HBM; factor left in HBM"},
             "pct_fp64_mfma_peak_per_gpu": 100.0 * value / world / (1e3 * FP64_MFMA_PEAK_TFLOPS),
             "device_ms_per_step": 1e3 * dev_s / args.steps,
-            "measured_update_kernel_TFLOPs_8192x8192x512": mf / 1e12 if mf > 0 else None,
-            "measured_update_kernel_TFLOPs_16384x16384x4096": mf_big / 1e12 if mf_big > 0 else None,
-            "measured_update_kernel_note": "k_update3 (one wave per 64x64 tile), the kernel of the big update regions; "
-                                           "k_update2 (four waves per tile, LDS-staged) on the large shape: %s TFLOP/s"
-                                           % (("%.1f" % (mf2_big / 1e12)) if mf2_big > 0 else "n/a"),
-            "measured_fp64_mfma_ceiling_TFLOPs": mpeak / 1e12 if mpeak > 0 else None,
-            "measured_fp64_mfma_ceiling_note": "best full-mantissa point of the inline-assembly MFMA loop (tools/mfma_ceiling.py): "
-                                               "the issue rate is 64 cycles per MFMA per SIMD = the 78.6 TFLOP/s spec at 2.4 GHz, "
-                                               "the figure is that rate at the clock the part sustains under the load",
-            "mfma_ceiling_sweep": sweep,
             "ms_per_step_resident": 1e3 * elapsed / args.steps,
-            "ms_per_step_api": 1e3 * elapsed_api / api_steps,
-            "value_api": fl * api_steps / elapsed_api / 1e9,
-            "pct_fp64_mfma_peak_api_per_gpu": 100.0 * fl * api_steps / elapsed_api / 1e12 / world / FP64_MFMA_PEAK_TFLOPS,
-            "value_note": "`value` / `ms_per_step` time the step with S = tril(PAP') already resident in HBM (the bench contract: inputs "
-                          "resident when the timed region starts); `value_api` / `ms_per_step_api` time cholmod_l_factorize (A, L, Common) "
-                          "with A in host memory (SURVEY 8d's t_factorize); the secondary lines quote the API step as their `value`",
-            "api_step": "cholmod_l_factorize(A, L, Common) called again on a matrix with the same pattern (hash of p / i "
-                        "checked on every call): H2D of A->x, gather into the resident S on the device, factorization on the "
-                        "cached plan, L left in HBM; a new pattern takes the host permutation + full upload again",
             "roofline": roof, "cpu_baseline": cpu,
             "host_seconds": {"generate": t_gen, "analyze": t_analyze, "plan_inside_analyze": t_plan,
                              "first_factorize_incl_plan_h2d": t_first, "analyze_plus_first_factorize": t_analyze + t_first},
         }
+        if args.full:
+            line.update({
+                "measured_update_kernel_TFLOPs_8192x8192x512": mf / 1e12 if mf > 0 else None,
+                "measured_update_kernel_TFLOPs_16384x16384x4096": mf_big / 1e12 if mf_big > 0 else None,
+                "measured_update_kernel_note": "k_update3 (one wave per 64x64 tile), the kernel of the big update regions; "
+                                               "k_update2 (four waves per tile, LDS-staged) on the large shape: %s TFLOP/s"
+                                               % (("%.1f" % (mf2_big / 1e12)) if mf2_big > 0 else "n/a"),
+                "measured_fp64_mfma_ceiling_TFLOPs": mpeak / 1e12 if mpeak > 0 else None,
+                "measured_fp64_mfma_ceiling_note": "best full-mantissa point of the inline-assembly MFMA loop (tools/mfma_ceiling.py): "
+                                                   "the issue rate is 64 cycles per MFMA per SIMD = the 78.6 TFLOP/s spec at 2.4 GHz, "
+                                                   "the figure is that rate at the clock the part sustains under the load",
+                "mfma_ceiling_sweep": sweep,
+                "ms_per_step_api": 1e3 * elapsed_api / api_steps,
+                "value_api": fl * api_steps / elapsed_api / 1e9,
+                "pct_fp64_mfma_peak_api_per_gpu": 100.0 * fl * api_steps / elapsed_api / 1e12 / world / FP64_MFMA_PEAK_TFLOPS,
+                "value_note": "`value` / `ms_per_step` time the step with S = tril(PAP') already resident in HBM (the bench contract: inputs "
+                              "resident when the timed region starts); `value_api` / `ms_per_step_api` time cholmod_l_factorize (A, L, Common) "
+                              "with A in host memory (SURVEY 8d's t_factorize); the secondary lines quote the API step as their `value`",
+                "api_step": "cholmod_l_factorize(A, L, Common) called again on a matrix with the same pattern (hash of p / i "
+                            "checked on every call): H2D of A->x, gather into the resident S on the device, factorization on the "
+                            "cached plan, L left in HBM; a new pattern takes the host permutation + full upload again",
+            })
         if resid is not None:
             line["residual_2norm"] = resid
             line["factor_checks"] = checks
@@ -1277,7 +1335,7 @@ def main():
                                 "all_gather_GB_waited_for_where_issued": 1e-9 * stats[39],
                                 "self_test_share_as_world": int(os.environ.get("CHOLMOD_HIP_SHARE_AS_WORLD", "0")) if selftest else None}
         if allreduce is not None:
-            nfac = max(args.steps + args.warmup + (0 if args.no_profile_pass else 1), 1)
+            nfac = max(args.steps + args.warmup + (1 if profile_pass else 0), 1)
             line["exchange"] = {"backend": args.dist_backend, "allreduce_calls_per_factorization": allreduce.stats["n"] // nfac,
                                 "allreduce_GB_per_factorization": 1e-9 * allreduce.stats["bytes"] / nfac,
                                 "allreduce_GB_by_group_size": {str(k): 1e-9 * v / nfac for k, v in sorted(allreduce.stats["by_size"].items())},

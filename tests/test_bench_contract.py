@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_json_line_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--grid", "24", "--steps", "2",
-                          "--warmup", "1", "--cpu-sample-m", "12", "--check"],
+                          "--warmup", "1", "--cpu-sample-m", "12", "--check", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -39,6 +39,52 @@ def test_bench_json_line_contract():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the run times its steps and prints the line, nothing else: no API step, profiled pass, solve, CPU
+    baseline or micro-benchmark.  --dump-outputs writes what the factor of the last timed step gives its caller, as float64
+    arrays well under 64 MB, and two runs with the same arguments write the same values."""
+    import numpy as np
+    from suitesparse_amd import generators as G
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--grid", "24", "--steps", "3",
+                              "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, out.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["dtype"] == "f64"
+        assert line["unit"] == "GFLOP/s" and line["higher_is_better"] is True and line["value"] > 0
+        assert line["roofline"] is None and line["cpu_baseline"] is None
+        for k_ in ("ms_per_step_api", "value_api", "residual_2norm", "factor_checks", "secondary", "measured_fp64_mfma_ceiling_TFLOPs"):
+            assert k_ not in line, k_
+        names = sorted(os.listdir(d))
+        assert names == ["factor_invariants.npy", "solution.npy"], names
+        arrs = {f: np.load(d / f) for f in names}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert sum(os.path.getsize(d / f) for f in names) <= 64e6
+        dumps.append(arrs)
+    n, Ap, Ai, Ax = G.poisson3d(24)
+    x = dumps[0]["solution.npy"]
+    assert x.shape == (n,)
+    b = G.demo_rhs(n)
+    assert np.linalg.norm(G.sym_matvec(n, Ap, Ai, Ax, -1, x) - b) / np.linalg.norm(b) < 1e-11
+    inv = dumps[0]["factor_invariants.npy"]
+    ld = G.poisson_logdet(24, 24, 24)
+    assert abs(2.0 * inv[0] - ld) / abs(ld) < 1e-11 and inv[1] == 0 and inv[2] == 0 and inv[4] == 0, inv
+    for f in dumps[0]:
+        np.testing.assert_allclose(dumps[1][f], dumps[0][f], rtol=1e-12, atol=0)
+
+
+def test_bench_options_full_and_dump_outputs_exist():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=120, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_over_gloo():
     """The N > 1 launch line of the driver (torch.distributed.run, one rank per GPU);
     on the 1-GPU box the two ranks share GPU 0 and exchange through gloo."""
@@ -47,7 +93,7 @@ def test_bench_two_ranks_over_gloo():
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port),
                           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--grid", "32", "--steps", "2", "--warmup", "1",
-                          "--dist-backend", "gloo", "--check"],
+                          "--dist-backend", "gloo", "--check", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -72,7 +118,7 @@ def test_bench_keeps_its_line_when_the_gathered_factor_does_not_fit():
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port),
                           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--grid", "24", "--steps", "1", "--warmup", "1",
-                          "--dist-backend", "gloo", "--check"],
+                          "--dist-backend", "gloo", "--check", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, CHOLMOD_HIP_TEST_FAIL_GATHER="1", SSAMD_TEST_HOOKS_LIB="1"))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -88,7 +134,7 @@ def test_bench_gpus_flag_launches_its_own_ranks():
     bench.py starts its two ranks itself and rank 0 prints the one line with n_gpus = 2."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--grid", "32",
-                          "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -149,7 +195,7 @@ def test_bench_exchange_selftest_at_100_cubed_over_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["CHOLMOD_HIP_SHARE_AS_WORLD"] = "8"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--grid", "100", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--no-cpu-baseline", "--no-secondary", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -179,7 +225,7 @@ def test_bench_exchange_selftest_at_the_headline_size_over_rccl(grid, extra):
     env["CHOLMOD_HIP_SHARE_AS_WORLD"] = "8"
     env.update(extra)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--grid", str(grid), "--steps", "1", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-secondary", "--no-profile-pass"], capture_output=True, text=True, timeout=1500,
+                          "--no-cpu-baseline", "--no-secondary", "--no-profile-pass", "--full"], capture_output=True, text=True, timeout=1500,
                          cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

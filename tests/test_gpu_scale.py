@@ -391,7 +391,7 @@ def test_bench_matrix_file_reader_path():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--matrix",
                           os.path.join(root, "tests", "golden", "bcsstk02.tri"), "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

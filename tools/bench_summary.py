@@ -38,7 +38,8 @@ if files:
         else:
             print(f, "NO JSON")
 else:
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + sys.argv[1:], capture_output=True, text=True)
+    args = sys.argv[1:] + ([] if "--full" in sys.argv[1:] else ["--full"])     # (the per-class seconds and secondary lines)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args, capture_output=True, text=True)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if not lines:
         print("NO JSON", out.stdout[-2000:], out.stderr[-3000:])

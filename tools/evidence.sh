@@ -8,9 +8,9 @@ TAG=${1:-r03x}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; cd $R
 if [[ " $* " == *" tests "* ]]; then
   python -m pytest tests -m gpu -q > $O/${TAG}_gpu_tests.log 2>&1; grep -E "passed|failed" $O/${TAG}_gpu_tests.log | tail -2
 fi
-python bench.py > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err
+python bench.py --full > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/${TAG}_stats_p200 --output-format csv -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary > $O/${TAG}_bench_line_rocprof_run.json 2> $O/${TAG}_stats_p200.err
+rocprofv3 --kernel-trace --stats -d $O/${TAG}_stats_p200 --output-format csv -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --full > $O/${TAG}_bench_line_rocprof_run.json 2> $O/${TAG}_stats_p200.err
 for W in "poisson3d 100 p100" "box3d 42 box42r3" "poisson2d 1259 p2d1259"; do set -- $W
   rocprofv3 --kernel-trace --stats -d $O/${TAG}_stats_$3 --output-format csv -- python $R/tools/one_factorization.py --workload $1 --grid $2 --repeat 3 > $O/${TAG}_stats_$3.log 2>&1
 done
