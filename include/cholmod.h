@@ -383,6 +383,11 @@ int cholmod_l_factor_to_host (cholmod_factor *L, cholmod_common *Common) ;
 /* Device time and per-class statistics of the last factorization
  * (CHOLMOD_HIP_NSTATS doubles, see cholmod_hip.h). */
 int cholmod_l_hip_stats (cholmod_factor *L, double *stats, cholmod_common *Common) ;
+/* Where the relaxed fronts of an analysed L hold explicit zeros (cholmod_hip_plan_create_reach's reach_p / reach_first for
+ * A's pattern and L's permutation): fills reach_p [0 .. nsuper] and, if reach_first is not NULL, reach_first; returns the
+ * length of reach_first, -1 on invalid input.  cholmod_l_analyze computes the same for the plan it builds. */
+int64_t cholmod_l_hip_front_reach (cholmod_sparse *A, cholmod_factor *L, int64_t *reach_p, int32_t *reach_first,
+    cholmod_common *Common) ;
 /* Create the device plan of a symbolic factor now (HBM reservation for L and the
  * contribution blocks) instead of at the first numeric factorization; FALSE with
  * CHOLMOD_OUT_OF_MEMORY if the device cannot hold it. */

@@ -108,6 +108,15 @@ cholmod_hip_plan *cholmod_hip_plan_create (int64_t n, int64_t nsuper,
 
 void cholmod_hip_plan_destroy (cholmod_hip_plan *plan) ;
 
+/* The same plan (one GPU) with what the analysis knows of the explicit zeros of the relaxed fronts: for every supernode s
+ * with reach_p [s+1] > reach_p [s] (= its row count), reach_first [reach_p [s] + p] is the first column of s, counted from
+ * its first column, whose pattern in L holds the row at position p of its row list (INT32_MAX: none).  The plan gives
+ * the big ones a head -- a first outer block of H columns whose closing update runs over the rows those columns reach
+ * only -- where that pays (stats [40]).  reach_p == NULL: exactly the plan of cholmod_hip_plan_create. */
+cholmod_hip_plan *cholmod_hip_plan_create_reach (int64_t n, int64_t nsuper,
+    const int64_t *super, const int64_t *pi, const int64_t *px,
+    const int64_t *s, int flags, const int64_t *reach_p, const int32_t *reach_first, int *status) ;
+
 /* ---- multi-GPU (one process per GPU; no counterpart in the reference, which is
  * single-GPU: CHOLMOD/GPU/cholmod_gpu.c:160-164) -------------------------------
  * Every rank builds the same plan from the same symbolic factor and passes its
@@ -310,9 +319,11 @@ int cholmod_hip_factor_checks_local (cholmod_hip_plan *plan, double *out5) ;
  *       plus the windows of the shared fronts (= [5] with one rank)
  *  [37] block columns of distributed fronts opened into their windows   [38] those whose window has a negative
  *       virtual base (the window is addressed as if the whole front were there: tests make sure both signs occur)
+ *  [40] algorithmic flops the head updates leave out: the products of rows the head does not reach (exact zeros); not in
+ *       [34] nor executed, still in [1]
  * Per-class seconds are only collected when profiling is enabled with
  * cholmod_hip_set_profiling(plan, 1) (it serialises the stream with events). */
-#define CHOLMOD_HIP_NSTATS 40
+#define CHOLMOD_HIP_NSTATS 41
 int cholmod_hip_get_stats (cholmod_hip_plan *plan, double *stats) ;
 int cholmod_hip_set_profiling (cholmod_hip_plan *plan, int on) ;
 /* The launch list of the plan and, after a factorization with profiling on, the

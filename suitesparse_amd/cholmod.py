@@ -20,7 +20,7 @@ HOOKS_LIB_PATH = os.path.join(_HERE, "lib", "libcholmod_amd_testhooks.so")
 CSRC = os.path.join(_HERE, "csrc")
 
 CHOLMOD_MAXMETHODS = 9
-CHOLMOD_HIP_NSTATS = 40
+CHOLMOD_HIP_NSTATS = 41
 
 # constants (include/cholmod.h)
 PATTERN, REAL, COMPLEX, ZOMPLEX = 0, 1, 2, 3
@@ -140,12 +140,12 @@ API_SYMBOLS = [
     "cholmod_l_gpu_memorysize", "cholmod_l_gpu_probe", "cholmod_l_gpu_deallocate",
     "cholmod_l_gpu_end", "cholmod_l_gpu_allocate",
     "cholmod_l_factor_to_host", "cholmod_l_hip_stats", "cholmod_l_refactorize_resident",
-    "cholmod_l_gather_factor", "cholmod_l_hip_prepare",
+    "cholmod_l_gather_factor", "cholmod_l_hip_prepare", "cholmod_l_hip_front_reach",
 ]
 HIP_SYMBOLS = [
     "cholmod_hip_probe", "cholmod_hip_memorysize", "cholmod_hip_set_device", "cholmod_hip_device_count",
     "cholmod_hip_plan_create", "cholmod_hip_plan_destroy", "cholmod_hip_factorize",
-    "cholmod_hip_plan_create_dist", "cholmod_hip_set_allreduce", "cholmod_hip_get_partition",
+    "cholmod_hip_plan_create_dist", "cholmod_hip_plan_create_reach", "cholmod_hip_set_allreduce", "cholmod_hip_get_partition",
     "cholmod_hip_get_groups", "cholmod_hip_get_batches", "cholmod_hip_progress_enable", "cholmod_hip_progress", "cholmod_hip_debug_schedule_hash", "cholmod_hip_diag_minmax", "cholmod_hip_values_staging", "cholmod_hip_values_push", "cholmod_hip_values_commit", "cholmod_hip_values_gather_index", "cholmod_hip_values_begin", "cholmod_hip_values_push_chunk", "cholmod_hip_debug_routing",
     "cholmod_hip_gather_factor",
     "cholmod_hip_upload_matrix", "cholmod_hip_factorize_resident",
@@ -259,6 +259,8 @@ def lib(hooks=None):
     sig("cholmod_hip_plan_destroy", None, [vp])
     sig("cholmod_hip_plan_create_dist", vp, [i64, i64, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int,
                                              C.POINTER(C.c_int)])
+    sig("cholmod_hip_plan_create_reach", vp, [i64, i64, vp, vp, vp, vp, C.c_int, vp, vp, C.POINTER(C.c_int)])
+    sig("cholmod_l_hip_front_reach", i64, [sp, fc, vp, vp, cm])
     sig("cholmod_hip_set_allreduce", C.c_int, [vp, ALLREDUCE_FN, vp])
     sig("cholmod_hip_get_partition", C.c_int, [vp, vp])
     sig("cholmod_hip_get_groups", C.c_int, [vp, vp, vp])

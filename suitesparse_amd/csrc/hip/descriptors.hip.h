@@ -89,6 +89,13 @@ struct GemmGroup {
                                 // front, dealt so that it evens out what the members' own slabs differ by
 };
 
+// A region of a front's head update restricted to the rows the head reaches (schedule_dense.hip: the head of a front): the
+// region's rows AND columns are the entries map .. map + g.m of the schedule's row-map array, in pairs (2t, 2t + 1) that
+// are adjacent rows of the front (map [2t + 1] == map [2t] + 1) -- only a last single entry may lack its partner.  Row i of
+// the region is row map [i] of the front: A (i, k) = Lx [a_off + map [i] + k lda], C (i, j) = (CB or Lx) [c_off + map [i] +
+// map [j] ldc]; its columns are the first g.n entries of the same list (the region starts on the diagonal, g.tri = 1).
+struct GatherGroup { GemmGroup g; i64 map; i32 tile_start; i32 pad; };
+
 // Contribution blocks of the generic fronts are stored as full squares, ld = ncb
 // (lower part used); those of the thin fronts as packed lower triangles:
 // element (i,j), i >= j, of a packed triangle of order m lives at tri_col(j,m) + i.

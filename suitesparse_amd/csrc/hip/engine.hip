@@ -71,7 +71,8 @@ static void free_device (cholmod_hip_plan *P)
     void *ptrs [] = {P->d_Ls, P->d_fr, P->d_supermap, P->d_child, P->d_relmap, P->d_info,
         P->d_lvl_list, P->d_Lx, P->d_cb, P->d_zg, P->d_eg, P->d_pg, P->d_tg, P->d_tu_cnt, P->d_cdesc, P->d_smd, P->d_sp01, P->d_gg, P->d_sm,
         P->d_Sp, P->d_Si, P->d_Snz, P->d_Sx, P->d_amap, P->d_X, P->d_Y, P->d_perm, P->d_xchg, P->d_stage, P->d_ag, P->d_agf, P->d_Lx_full, P->d_fr_full, P->d_dg, P->d_rg, P->d_wg, P->d_cg, P->d_cflags, P->d_crel, P->d_relpairs, P->d_dinv, P->d_sv,
-        P->d_inv_tasks, P->d_winv, P->d_solved, P->d_sv_acc, P->d_ticket, P->d_chk, P->d_chk_out, P->d_thin_tim, P->d_sb_tasks, P->d_sb_commit, P->d_first_fail, P->d_vsrc, P->d_vals} ;
+        P->d_inv_tasks, P->d_winv, P->d_solved, P->d_sv_acc, P->d_ticket, P->d_chk, P->d_chk_out, P->d_thin_tim, P->d_sb_tasks, P->d_sb_commit, P->d_first_fail, P->d_vsrc, P->d_vals,
+        P->d_xg, P->d_gmap} ;
     for (void *p : ptrs) if (p) (void) hipFree (p) ;
     for (auto e : P->evpool) (void) hipEventDestroy (e) ;
     for (auto e : P->sync_ev) (void) hipEventDestroy (e) ;
@@ -159,6 +160,8 @@ static int upload_plan (cholmod_hip_plan *P)
     P->d_rg = dupload (P->sch.rg, e) ; HIPCHK (e) ;
     P->d_wg = dupload (P->sch.wg, e) ; HIPCHK (e) ;
     P->d_cg = dupload (P->sch.cg, e) ; HIPCHK (e) ;
+    P->d_xg = dupload (P->sch.xg, e) ; HIPCHK (e) ;
+    P->d_gmap = dupload (P->sch.gmap, e) ; HIPCHK (e) ;
     HIPCHK (hipMalloc ((void **) &P->d_cflags, (4 * (size_t) P->sch.ncflags + 4) * sizeof (int))) ;
     HIPCHK (hipMalloc ((void **) &P->d_dinv, (size_t) std::max (P->sch.max_dinv_slots, 1) * 4096 * sizeof (double))) ;
     P->d_sm = dupload (P->sch.sm, e) ; HIPCHK (e) ;
@@ -500,6 +503,17 @@ static int run_launch (cholmod_hip_plan *P, const Launch &L, bool serial)
             else if (L.aux >= 1024) TW_LAUNCH (k_update3<4 COMMA, >, dim3 (L.grid), dim3 (64), 0, st, P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
             else TW_LAUNCH (k_update3<2 COMMA, >, dim3 (L.grid), dim3 (64), 0, st, P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
             break ;
+        case K_UPD_G:
+            // head updates over the rows their heads reach (schedule_dense.hip: add_head_gathered), sized as K_UPD_W
+            if (L.half)
+            {
+                const unsigned gh = 2u * (unsigned) ((L.grid + 7) / 8 * 8) ;
+                if (L.aux >= 1024) hipLaunchKernelGGL ((k_update3g<4, true>), dim3 (gh), dim3 (64), 0, st, P->d_xg + L.goff, L.ng, P->d_gmap, P->d_Lx, P->d_cb) ;
+                else hipLaunchKernelGGL ((k_update3g<2, true>), dim3 (gh), dim3 (64), 0, st, P->d_xg + L.goff, L.ng, P->d_gmap, P->d_Lx, P->d_cb) ;
+            }
+            else if (L.aux >= 1024) hipLaunchKernelGGL ((k_update3g<4, false>), dim3 (L.grid), dim3 (64), 0, st, P->d_xg + L.goff, L.ng, P->d_gmap, P->d_Lx, P->d_cb) ;
+            else hipLaunchKernelGGL ((k_update3g<2, false>), dim3 (L.grid), dim3 (64), 0, st, P->d_xg + L.goff, L.ng, P->d_gmap, P->d_Lx, P->d_cb) ;
+            break ;
         case K_UPD_PF:
             TW_LAUNCH (k_update2f<, >, dim3 (L.grid), dim3 (256), 0, st,
                 P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb, P->d_info) ;
@@ -773,7 +787,8 @@ static int run_factorize (cholmod_hip_plan *P, double beta, int quick, i64 *mino
     {
         const Launch &L = P->sch.launches [q] ;
         if (L.kind == K_UPD_SMALL) { S [7] += 1 ; S [8] += L.flops ; S [16] += L.bytes ; }
-        if (L.kind == K_UPD_W) { S [33] += 1 ; S [34] += L.flops ; S [35] += L.bytes ; }
+        if (L.kind == K_UPD_W || L.kind == K_UPD_G) { S [33] += 1 ; S [34] += L.flops ; S [35] += L.bytes ; }
+        if (L.kind == K_UPD_G) S [40] += L.skipped ;
         if (L.kind == K_UPD_PF) { S [26] += 1 ; S [28] += L.flops ; S [29] += L.bytes ; }
         if (L.kind == K_TRSM_UPD) S [31] += 1 ;
         if (L.kind == K_SMALL) { S [20] += L.bytes ; S [21] += L.ng ; }
@@ -803,7 +818,7 @@ static int run_factorize (cholmod_hip_plan *P, double beta, int quick, i64 *mino
             {
                 case K_UPD_SMALL: S [6] += sec ; if (L.aux < MB) { S [23] += sec ; } break ;
                 case K_UPD_PF: S [27] += sec ; break ;
-                case K_UPD_W: S [32] += sec ; break ;
+                case K_UPD_W: case K_UPD_G: S [32] += sec ; break ;
                 case K_UPD_BIG: S [14] += sec ; break ;
                 case K_EA: case K_ZERO: case K_WIN: S [9] += sec ; break ;
                 case K_POTRF: case K_DIAG: case K_CHAINF: S [11] += sec ; break ;
@@ -906,7 +921,7 @@ int cholmod_hip_set_device (int device)
 
 static cholmod_hip_plan *plan_create_impl (int64_t n, int64_t nsuper,
     const int64_t *super, const int64_t *pi, const int64_t *px, const int64_t *s,
-    int flags, int rank, int world, int *status) ;
+    int flags, int rank, int world, int *status, const int64_t *reach_p = nullptr, const int32_t *reach_first = nullptr) ;
 
 cholmod_hip_plan *cholmod_hip_plan_create_dist (int64_t n, int64_t nsuper,
     const int64_t *super, const int64_t *pi, const int64_t *px, const int64_t *s,
@@ -919,9 +934,19 @@ cholmod_hip_plan *cholmod_hip_plan_create_dist (int64_t n, int64_t nsuper,
     catch (const std::bad_alloc &) { *status = CHOLMOD_HIP_OUT_OF_MEMORY ; return nullptr ; }
 }
 
+cholmod_hip_plan *cholmod_hip_plan_create_reach (int64_t n, int64_t nsuper,
+    const int64_t *super, const int64_t *pi, const int64_t *px, const int64_t *s,
+    int flags, const int64_t *reach_p, const int32_t *reach_first, int *status)
+{
+    int st_local ;
+    if (!status) status = &st_local ;
+    try { return plan_create_impl (n, nsuper, super, pi, px, s, flags, 0, 1, status, reach_p, reach_first) ; }
+    catch (const std::bad_alloc &) { *status = CHOLMOD_HIP_OUT_OF_MEMORY ; return nullptr ; }
+}
+
 static cholmod_hip_plan *plan_create_impl (int64_t n, int64_t nsuper,
     const int64_t *super, const int64_t *pi, const int64_t *px, const int64_t *s,
-    int flags, int rank, int world, int *status)
+    int flags, int rank, int world, int *status, const int64_t *reach_p, const int32_t *reach_first)
 {
     *status = CHOLMOD_HIP_OK ;
     if (n < 0 || nsuper < 0 || !super || !pi || !px || !s || world < 1 || rank < 0 || rank >= world)
@@ -964,6 +989,18 @@ static cholmod_hip_plan *plan_create_impl (int64_t n, int64_t nsuper,
     P->px.assign (px, px + nsuper + 1) ;
     P->ssize = pi [nsuper] ; P->xsize = px [nsuper] ;
     P->Ls.assign (s, s + std::max<i64> (P->ssize, 1)) ;
+    if (reach_p && reach_first)
+    {
+        // (a front the analysis looked at has one entry per row of its row list, the others none)
+        for (i64 q = 0 ; q < nsuper ; q++)
+        {
+            const i64 len = reach_p [q + 1] - reach_p [q] ;
+            if (len < 0 || (len != 0 && len != pi [q + 1] - pi [q])) { *status = CHOLMOD_HIP_INVALID ; return nullptr ; }
+        }
+        P->reach_p.assign (reach_p, reach_p + nsuper + 1) ;
+        P->reach_first.assign (reach_first + reach_p [0], reach_first + reach_p [nsuper]) ;
+        for (i64 &v : P->reach_p) v -= reach_p [0] ;
+    }
     // memory budget of the contribution-block arena (see build_host): what is left
     // of the HBM next to L and the index maps.  Several ranks must derive the same
     // schedule, so they use a nominal capacity instead of their momentary free
@@ -1976,7 +2013,10 @@ int cholmod_hip_debug_schedule_hash (cholmod_hip_plan *P, uint64_t *out16)
     } ;
     const Schedule &S = P->sch ;
     out16 [0] = hv (S.zg) ; out16 [1] = hv (S.eg) ; out16 [2] = hv (S.pg) ; out16 [3] = hv (S.tg) ;
-    out16 [4] = hv (S.gg) ; out16 [5] = hv (S.dg) ; out16 [6] = hv (S.rg) ; out16 [7] = hv (S.wg) ;
+    out16 [4] = hv (S.gg) ;
+    // (gathered head regions and their row maps: folded in only where a plan has them, so plans without heads hash as before)
+    if (!S.xg.empty ()) out16 [4] = fnv (fnv (out16 [4], S.xg.data (), S.xg.size () * sizeof (GatherGroup)), S.gmap.data (), S.gmap.size () * sizeof (i32)) ;
+    out16 [5] = hv (S.dg) ; out16 [6] = hv (S.rg) ; out16 [7] = hv (S.wg) ;
     out16 [8] = hv (S.cg) ; out16 [9] = hv (S.sm) ;
     uint64_t h = H0 ;
     for (const Launch &L : S.launches)

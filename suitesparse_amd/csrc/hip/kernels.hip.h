@@ -1886,9 +1886,15 @@ __global__ void __launch_bounds__(256, MINW) k_update2 (const GemmGroup *g, int 
 #ifndef UPD3_CLAMP_LOADS
 #define UPD3_CLAMP_LOADS 0
 #endif
-template <int DEPTH, bool EDGE, int TW = 0, int NQ = 2>
-__device__ __forceinline__ void update_tile_w (const GemmGroup &G, int I, int J, double *Lx, double *CB, int cofs = 0)
+// GATHER: a region of a head update restricted to the rows the head reaches (descriptors.hip.h: GatherGroup).  A lane's row
+// pairs and the epilogue's rows and columns are looked up in the region's row map once per tile; the k-loop, its loads and the
+// MFMA order are those of the plain tile (every pair of the map is a pair of adjacent rows of the front), so an entry the
+// gathered tile computes is bit for bit what the plain tile computes there.
+template <int DEPTH, bool EDGE, int TW = 0, int NQ = 2, bool GATHER = false>
+__device__ __forceinline__ void update_tile_w (const GemmGroup &G, int I, int J, double *Lx, double *CB, int cofs = 0,
+    const i32 *rmap = nullptr)
 {
+    static_assert (!GATHER || (TW == 0 && !UPD3_CLAMP_LOADS), "a gathered tile is real and loads row pairs") ;
     const int lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4 ;
     const int row0 = I * 64, col0 = J * 64 + cofs ;
     const int mrem = G.m - row0, nrem = G.n - col0 ;
@@ -1911,8 +1917,19 @@ __device__ __forceinline__ void update_tile_w (const GemmGroup &G, int I, int J,
                 if (rb [q][h] > nrem - 1) rb [q][h] = nrem - 1 ;
             }
         }
-        pa [q] = Lx + G.a_off + row0 + (i64) lk * lda ;
-        pb [q] = Lx + G.b_off + col0 + (i64) lk * lda ;
+        if constexpr (GATHER)
+        {
+            // (rows past the region's edge read the last pair of the map: they feed accumulators nobody stores)
+            const int ia = min (row0 + ra [q][0], G.m - 1), ib = min (col0 + rb [q][0], G.n - 1) ;
+            pa [q] = Lx + G.a_off + rmap [ia] + (i64) lk * lda ;
+            pb [q] = Lx + G.b_off + rmap [ib] + (i64) lk * lda ;
+            ra [q][0] = rb [q][0] = 0 ; ra [q][1] = rb [q][1] = 1 ;
+        }
+        else
+        {
+            pa [q] = Lx + G.a_off + row0 + (i64) lk * lda ;
+            pb [q] = Lx + G.b_off + col0 + (i64) lk * lda ;
+        }
     }
     struct Frag { double a [4], b [2 * NQ] ; } ;     // a [2 q + h] = A (row pair q, member h), likewise b (NQ column pairs)
     // a full k-step (columns kk .. kk + 3 all below K)
@@ -2029,6 +2046,13 @@ __device__ __forceinline__ void update_tile_w (const GemmGroup &G, int I, int J,
     // epilogue: acc [a][b][r] of lane (lr, lk) is C (row 32 (a >> 1) + 2 lr + (a & 1),
     // column 32 (b >> 1) + 2 (lk + 4 r) + (b & 1))
     double *C = (G.c_in_cb ? CB : Lx) + G.c_off + row0 + colx<TW == 2> (col0, G.ldc) ;
+    double *Cg = GATHER ? (G.c_in_cb ? CB : Lx) + G.c_off : nullptr ;      // (gathered: rows and columns through the map)
+    int rg [2] = {0, 0} ;
+    if constexpr (GATHER)
+    {
+#pragma unroll
+        for (int q = 0 ; q < 2 ; q++) rg [q] = rmap [min (row0 + 32 * q + 2 * lr, G.m - 1)] ;
+    }
     const bool diag = G.tri && I == J ;
 #pragma unroll
     for (int b = 0 ; b < 2 * NQ ; b++)
@@ -2038,11 +2062,12 @@ __device__ __forceinline__ void update_tile_w (const GemmGroup &G, int I, int J,
             if (TW == 2 && (b & 1)) continue ;          // (complex storage: the even twin columns only)
             const int j = 32 * (b >> 1) + 2 * (lk + 4 * r) + (b & 1) ;      // column inside this wave's part of the tile
             const int jd = j + cofs ;                                       // ... inside the tile (the diagonal test)
-            double *Cj = C + colx<TW == 2> (j, G.ldc) ;
+            double *Cj = GATHER ? Cg + (i64) rmap [min (col0 + j, G.n - 1)] * G.ldc : C + colx<TW == 2> (j, G.ldc) ;
 #pragma unroll
             for (int q = 0 ; q < 2 ; q++)
             {
                 const int i = 32 * q + 2 * lr ;
+                const int io = GATHER ? rg [q] : i ;        // where row i of the tile lives in column Cj
                 // the row pair (i, i + 1) of column j, both rows inside the region
                 auto store_pair = [&] ()
                 {
@@ -2051,11 +2076,11 @@ __device__ __forceinline__ void update_tile_w (const GemmGroup &G, int I, int J,
                     if (G.assign) { v.x = -acc [2 * q][b][r] ; v.y = -acc [2 * q + 1][b][r] ; }
                     else
                     {
-                        v = *(const d2u *) (Cj + i) ;
+                        v = *(const d2u *) (Cj + io) ;
                         v.x -= acc [2 * q][b][r] ; v.y -= acc [2 * q + 1][b][r] ;
                     }
-                    if (diag && i < jd) Cj [i + 1] = v.y ;          // (the pair straddles the diagonal)
-                    else *(d2u *) (Cj + i) = v ;
+                    if (diag && i < jd) Cj [io + 1] = v.y ;         // (the pair straddles the diagonal)
+                    else *(d2u *) (Cj + io) = v ;
                 } ;
                 if constexpr (EDGE)
                 {
@@ -2066,8 +2091,8 @@ __device__ __forceinline__ void update_tile_w (const GemmGroup &G, int I, int J,
                         if (i + 1 < mrem) store_pair () ;
                         else if (i < mrem && (!diag || i >= jd))
                         {
-                            if (G.assign) Cj [i] = -acc [2 * q][b][r] ;
-                            else Cj [i] -= acc [2 * q][b][r] ;
+                            if (G.assign) Cj [io] = -acc [2 * q][b][r] ;
+                            else Cj [io] -= acc [2 * q][b][r] ;
                         }
                     }
                 }
@@ -2106,6 +2131,33 @@ __global__ void __launch_bounds__(64 * WPB, 2) k_update3 (const GemmGroup *g, in
     {
         if (G.m - I * 64 >= 64 && G.n - J * 64 >= 64) update_tile_w<DEPTH, false, TW> (G, I, J, Lx, CB) ;
         else update_tile_w<DEPTH, true, TW> (G, I, J, Lx, CB) ;
+    }
+}
+
+// The head update of a front restricted to the rows the head reaches (GatherGroup; schedule_dense.hip): k_update3 on the
+// region's row map, whole tiles or HALF tiles as above.
+template <int DEPTH, bool HALF = false>
+__global__ void __launch_bounds__(64, 2) k_update3g (const GatherGroup *g, int ng, const i32 *rmap, double *Lx, double *CB)
+{
+    int vb = (int) blockIdx.x ;
+    int cofs = 0 ;
+    if constexpr (HALF) { cofs = ((vb >> 3) & 1) * 32 ; vb = ((vb >> 4) << 3) | (vb & 7) ; }
+    const int gi = find_group (g, ng, vb, &GatherGroup::tile_start) ;
+    const GemmGroup G = g [gi].g ;
+    const i32 *map = rmap + g [gi].map ;
+    int I, J ;
+    if (vb - G.tile_start >= G.nblk) return ;
+    if (!decode_tile (G, vb - G.tile_start, I, J)) return ;
+    if constexpr (HALF)
+    {
+        if (G.n - J * 64 - cofs <= 0) return ;
+        if (G.m - I * 64 >= 64 && G.n - J * 64 - cofs >= 32) update_tile_w<DEPTH, false, 0, 1, true> (G, I, J, Lx, CB, cofs, map) ;
+        else update_tile_w<DEPTH, true, 0, 1, true> (G, I, J, Lx, CB, cofs, map) ;
+    }
+    else
+    {
+        if (G.m - I * 64 >= 64 && G.n - J * 64 >= 64) update_tile_w<DEPTH, false, 0, 2, true> (G, I, J, Lx, CB, 0, map) ;
+        else update_tile_w<DEPTH, true, 0, 2, true> (G, I, J, Lx, CB, 0, map) ;
     }
 }
 

@@ -76,7 +76,7 @@ static inline int window_count (const FrontD &f, int ob) { return f.nscol > ob ?
 // K_XCHG_RS / K_XCHG_AG: the exchange of a shared front's block column (multi-GPU): reduce-scatter of
 // the partial sums by row chunks before its panel chain, all-gathers of the solved chunks after it (near rows in line,
 // far rows on the exchange stream, awaited by a K_JOIN ahead of the outer update)
-enum Kind { K_ZERO = 0, K_EA, K_POTRF, K_TRSM, K_UPD_BIG, K_UPD_SMALL, K_JOIN, K_XCHG_RS, K_SMALL, K_UPD_PF, K_TRSM_UPD, K_XCHG_AG, K_UPD_W, K_DIAG, K_ROWSOLVE, K_WIN, K_CHAINF, K_NKIND } ;
+enum Kind { K_ZERO = 0, K_EA, K_POTRF, K_TRSM, K_UPD_BIG, K_UPD_SMALL, K_JOIN, K_XCHG_RS, K_SMALL, K_UPD_PF, K_TRSM_UPD, K_XCHG_AG, K_UPD_W, K_DIAG, K_ROWSOLVE, K_WIN, K_CHAINF, K_UPD_G, K_NKIND } ;
 
 struct Launch {
     int kind ;
@@ -96,6 +96,7 @@ struct Launch {
     int leaf_pw = 0 ;               // K_SMALL: every front is a leaf of <= 32 rows and <= leaf_pw (4/8/12/16) columns: two per wave (k_leaf_pair)
     int ndiag = 0 ;                 // K_CHAINF: diagonal workgroups of the launch (they come first in the grid)
     int half = 0 ;                  // K_UPD_W: two waves per 64 x 64 tile, 64 x 32 each (k_update3<..., HALF>): launches of 512 .. 10 240 tiles
+    double skipped = 0 ;            // K_UPD_G: algorithmic flops of the rows the heads do not reach (not executed)
 } ;
 
 #define HIPCHK(call) do { hipError_t e_ = (call) ; if (e_ != hipSuccess) { \
@@ -180,6 +181,8 @@ struct Schedule {
     std::vector<RsGroup> rg ;       // k_rowsolve: the rows below them
     std::vector<WinD> wg ;          // k_win_move: block columns of distributed fronts into / out of their windows
     std::vector<CfGroup> cg ;       // k_chainf: the 256-column chain in one launch (diagonal + row workgroups, flags)
+    std::vector<GatherGroup> xg ;   // k_update3g: head updates restricted to the rows their heads reach
+    std::vector<i32> gmap ;         // ... their row maps (GatherGroup::map indexes this)
     int ncflags = 0 ;               // flag slots (one per front and sub-block column of the whole schedule)
     int max_dinv_slots = 0 ;        // most diagonal sub-blocks in one launch (size of the inverse buffer)
     std::vector<i32> sm ;           // front ids handled by the fused small-front kernel
@@ -284,6 +287,13 @@ struct cholmod_hip_plan {
     double *d_chk_out = nullptr ;
     Schedule sch ;
     double exec_flops = 0 ;
+    // Heads (one GPU, real plans from cholmod_hip_plan_create_reach): reach_first [reach_p [s] + p] = first column of front s
+    // that reaches its row p (INT32_MAX: none), for the fronts the analysis looked at (reach_p [s + 1] > reach_p [s]);
+    // head [s] = width of the first outer block of front s (0: none, every outer block OB wide from column 0)
+    std::vector<i64> reach_p ;
+    std::vector<i32> reach_first, head ;
+    bool head_gather = true ;               // the head update over the rows it reaches only (CHOLMOD_HIP_HEAD_NO_GATHER: all rows)
+    GatherGroup *d_xg = nullptr ; i32 *d_gmap = nullptr ;
     // device
     hipStream_t stream = nullptr ;          // main stream
     hipStream_t stream2 = nullptr ;         // exchange stream (exchange look-ahead of a shared front's next block column)
@@ -368,12 +378,16 @@ struct cholmod_hip_plan {
 
 namespace sship {
 
+// what schedule_dense needs of the heads of a plan (cholmod_hip_plan::head, reach_p, reach_first)
+struct HeadInfo { const i32 *head ; const i64 *reach_p ; const i32 *first ; bool gather ; } ;
+
 // plan_build.hip: everything a rank derives from the symbolic factor on the host (supernodal etree, levels, ownership,
 // the rank's layout of L and of the arena, batches, launch list)
 int build_host (cholmod_hip_plan *P) ;
 // schedule_dense.hip: the launches of the dense partial factorization of one batch of fronts
 void schedule_dense (const std::vector<FrontD> &fr, const i32 *ids, int nf,
     Schedule &S, int flags, const i32 *owner, const i32 *grp0, const i32 *grpn, int rank, int world,
-    const char *assign_cb = nullptr, const i64 *win = nullptr, const i32 *child = nullptr, bool allow_half = false) ;
+    const char *assign_cb = nullptr, const i64 *win = nullptr, const i32 *child = nullptr, bool allow_half = false,
+    const HeadInfo *heads = nullptr) ;
 
 } // namespace sship

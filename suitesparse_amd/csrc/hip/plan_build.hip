@@ -765,9 +765,54 @@ struct PlanBuilder
             schedule_extend_add (ids, nf, 0) ;
             schedule_dense (P->fr, ids, nf, S, P->flags, P->owner.data (), P->grp0.data (), P->grpn.data (),
                 P->rank, P->world, P->assign_cb.data (), P->win_off.data (), P->child.data (),
-                P->world == 1 && !P->force_shared) ;      // (half tiles: one GPU -- plans of several ranks run four tiles per workgroup)
+                P->world == 1 && !P->force_shared,        // (half tiles: one GPU -- plans of several ranks run four tiles per workgroup)
+                P->head.empty () ? nullptr : &heads) ;
             schedule_extend_add (ids, nf, 1) ;
         }
+    }
+
+    // Heads (plans with reach information, cholmod_hip_plan_create_reach).  Relaxed amalgamation leaves explicit zeros in the
+    // big fronts: their leading columns (merged child separators) do not reach part of the trailing rows, so the update that
+    // closes a first outer block of H columns needs only the rows those columns reach (schedule_dense.hip: add_head_gathered).
+    // H (a multiple of 256 below the front's OB) is chosen per front by a price: the flops the head leaves out at the rate of
+    // the OB-wide update they would have been part of, against the head update at the rate of its shorter contraction and one
+    // more read-modify-write pass over the trailing matrix (the outer blocks after the head are OB wide from H on).  Rates: the
+    // one-wave-per-tile kernel inside the factorization by contraction length.  No head where the price
+    // is below 0.25 ms.  One GPU, real plans, fronts nobody shares; CHOLMOD_HIP_NO_HEADS: none at all; CHOLMOD_HIP_HEAD_ALL=1
+    // (tests): the head that leaves out the most flops on every front where one leaves out any, whatever the price.
+    HeadInfo heads {nullptr, nullptr, nullptr, true} ;
+    void choose_heads ()
+    {
+        P->head.clear () ;
+        if (P->reach_p.empty () || P->world != 1 || P->force_shared || getenv ("CHOLMOD_HIP_NO_HEADS")) return ;
+        if (P->flags & (CHOLMOD_HIP_PHI_TWIN | CHOLMOD_HIP_CX_STORAGE | CHOLMOD_HIP_TILE128)) return ;
+        const ObThresholds obt = outer_block_thresholds () ;
+        const bool all = getenv ("CHOLMOD_HIP_HEAD_ALL") && atoi (getenv ("CHOLMOD_HIP_HEAD_ALL")) != 0 ;
+        auto rate = [] (int K) { return 1e12 * (K < 512 ? 60.0 : K < 1024 ? 70.0 : K < 2048 ? 74.5 : 75.0) ; } ;
+        auto tri = [] (double m) { return m * (m + 1) / 2 ; } ;
+        std::vector<i32> head (P->nsuper, 0) ;
+        bool any = false ;
+        for (i64 s = 0 ; s < P->nsuper ; s++)
+        {
+            const FrontD &f = P->fr [s] ;
+            if (P->reach_p [s + 1] - P->reach_p [s] != f.nsrow || P->owner [s] < 0) continue ;
+            const i32 *first = P->reach_first.data () + P->reach_p [s] ;
+            const int OB = front_ob (f, P->flags, obt) ;
+            double best = all ? 0.0 : 0.25e-3 ;
+            for (int H = 256 ; H < std::min (OB, (int) f.nscol) ; H += 256)
+            {
+                i64 R = 0 ;
+                for (int p = H ; p < f.nsrow ; p++) R += first [p] < H ;
+                const double N = f.nsrow - H ;
+                const double gain = all ? 2.0 * H * (tri (N) - tri ((double) R))
+                    : 2.0 * H * tri (N) / rate (OB) - 2.0 * H * tri ((double) R) / rate (H) - 16.0 * tri (N) / 4e12 ;
+                if (gain > best) { best = gain ; head [s] = H ; any = true ; }
+            }
+        }
+        if (!any) return ;
+        P->head.swap (head) ;
+        P->head_gather = !getenv ("CHOLMOD_HIP_HEAD_NO_GATHER") ;
+        heads = HeadInfo {P->head.data (), P->reach_p.data (), P->reach_first.data (), P->head_gather} ;
     }
 
     int run ()
@@ -777,12 +822,15 @@ struct PlanBuilder
         rc = build_etree () ;
         if (rc != CHOLMOD_HIP_OK) return rc ;
         assign_ownership () ;
+        choose_heads () ;
         layout_local_factor () ;
         build_child_lists () ;
         choose_batches () ;
         build_solve_tasks () ;
         layout_windows () ;
         schedule_batches () ;
+        // (known from the plan alone: a host-only plan reports it too)
+        for (const Launch &L : P->sch.launches) P->stats [40] += L.skipped ;
         return CHOLMOD_HIP_OK ;
     }
 } ;

@@ -35,6 +35,7 @@ struct DenseScheduler
     const i64 *win ;                // window of a distributed front (offset in the rank's L), -1 / nullptr: none
     const i32 *child ;              // the rank's child lists (pricing of the extend-add into a window)
     const bool allow_half ;         // one GPU: launches of a few thousand tiles may run two waves per tile (below)
+    const HeadInfo *heads ;         // heads of the fronts (one GPU, real plans; nullptr: none)
     // ---- derived once per batch
     // The real twin of a complex factor (phi embedding, host/complex.c): every row / column pair (2i, 2i+1) is (re, im) of
     // one complex row, the odd columns of a panel are the rotations of the even ones.  The update kernels then contract over
@@ -74,6 +75,8 @@ struct DenseScheduler
     std::vector<GemmGroup> big, small ;     // regions collected for the next flush: 128 x 128 tiles (opt-in) / 64 x 64
     std::vector<GemmGroup> pfv ;            // narrow updates whose first tile is factored on the spot (k_update2f)
     std::vector<GemmGroup> wav ;            // regions big enough for one wave per 64 x 64 tile (k_update3)
+    std::vector<GatherGroup> gav ;          // head updates over the rows their heads reach (k_update3g)
+    double gav_skipped = 0 ;                // ... the flops they leave out
     std::vector<int> early ;                // block column of front q already summed ahead of time
     std::vector<int> early_open ;           // block column of front q opened (window) ahead of time
     std::vector<int> pf_done ;              // column whose diagonal block a fused update / solve has factored
@@ -81,9 +84,9 @@ struct DenseScheduler
 
     DenseScheduler (const std::vector<FrontD> &fr_, const i32 *ids_, int nf_, Schedule &S_, int flags_, const i32 *owner_,
         const i32 *grp0_, const i32 *grpn_, int rank_, int world_, const char *assign_cb_, const i64 *win_, const i32 *child_,
-        bool allow_half_)
+        bool allow_half_, const HeadInfo *heads_)
         : fr (fr_), ids (ids_), nf (nf_), S (S_), flags (flags_), owner (owner_), grp0 (grp0_), grpn (grpn_), rank (rank_),
-          world (world_), assign_cb (assign_cb_), win (win_), child (child_), allow_half (allow_half_)
+          world (world_), assign_cb (assign_cb_), win (win_), child (child_), allow_half (allow_half_), heads (heads_)
     {
         cx = (flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;
         twin = (flags & CHOLMOD_HIP_PHI_TWIN) != 0 || cx ;
@@ -122,6 +125,18 @@ struct DenseScheduler
     // Outer block width: a property of the FRONT (its row count), not of the batch -- the ranks of a multi-GPU group see
     // different batches around the same shared front and must cut its updates into the same regions.
     int ob_of (const FrontD &f) const { return front_ob (f, flags, obt) ; }
+    // A front with a head (plan_build.hip: choose_heads; never a shared or distributed one) has the outer blocks [0, H), then
+    // OB-wide ones from H on; every other front OB-wide ones from 0.  [o0, o1) = the outer block that holds column i0.
+    int head_of (int fid) const { return heads && heads->head ? heads->head [fid] : 0 ; }
+    void ob_bounds (int q, int i0, int &o0, int &o1) const
+    {
+        const FrontD &f = fr [ids [q]] ;
+        const int OBq = ob_of (f), H = head_of (ids [q]) ;
+        if (H > 0 && i0 < H) o0 = 0 ;
+        else if (H > 0) o0 = H + ((i0 - H) / OBq) * OBq ;
+        else o0 = (i0 / OBq) * OBq ;
+        o1 = std::min (o0 + (H > 0 && i0 < H ? H : OBq), (int) f.nscol) ;
+    }
     // (owner [] < 0 only occurs with world > 1, or in the single-rank self test CHOLMOD_HIP_SHARE_AS_WORLD that drives the
     // exchange path with one rank)
     bool is_shared (int fid) const { return owner && owner [fid] < 0 ; }
@@ -421,6 +436,84 @@ struct DenseScheduler
         flush_kind (small, K_UPD_SMALL) ;
         flush_kind (pfv, K_UPD_PF) ;
         flush_kind (wav, K_UPD_W) ;
+        flush_gathered () ;
+    }
+    // The update that closes the head [0, H) of front q -- everything to its right, contribution block included -- over the
+    // rows the head reaches only: an entry of another row is a sum of products with exact zeros.  Two regions on row maps
+    // (GatherGroup): the in-front columns with every row below them, paired from H on, and the contribution block, paired
+    // from nscol on; a pair is taken when either of its rows is reached.  The contribution block is cleared first when this
+    // update is the one that would have assigned it.
+    void add_head_gathered (const Upd &x)
+    {
+        const int fid = ids [x.q], H = x.kk ;
+        const FrontD &f = fr [fid] ;
+        const i32 *first = heads->first + heads->reach_p [fid] ;
+        auto tri_elems = [] (double m, double n) { return n * (n + 1) / 2 + (m - n) * n ; } ;
+        double full = tri_elems (f.nsrow - H, f.nscol - H) + tri_elems (f.ncb, f.ncb), done = 0 ;
+        auto gathered = [&] (int from, int ncols, bool to_cb)
+        {
+            const size_t m0 = S.gmap.size () ;
+            int n = 0 ;
+            for (int p = from ; p < f.nsrow ; p += 2)
+            {
+                if (first [p] >= H && (p + 1 >= f.nsrow || first [p + 1] >= H)) continue ;
+                S.gmap.push_back (p) ; n += p < from + ncols ;
+                if (p + 1 < f.nsrow) { S.gmap.push_back (p + 1) ; n += p + 1 < from + ncols ; }
+            }
+            const int m = (int) (S.gmap.size () - m0) ;
+            if (n == 0) { S.gmap.resize (m0) ; return ; }
+            GatherGroup X ;
+            memset (&X, 0, sizeof (X)) ;
+            X.g = blank_region (fid) ;
+            X.g.a_off = X.g.b_off = f.psx ; X.g.lda = f.nsrow ;
+            if (to_cb) { X.g.c_off = f.cb - f.nscol - (i64) f.nscol * f.ncb ; X.g.ldc = f.ncb ; X.g.c_in_cb = 1 ; }
+            else { X.g.c_off = f.psx ; X.g.ldc = f.nsrow ; }
+            X.g.m = m ; X.g.n = n ; X.g.k = H ; X.g.tri = 1 ;
+            X.g.assign = (to_cb && assign_cb && assign_cb [fid]) ? 1 : 0 ;
+            X.map = (i64) m0 ;
+            done += tri_elems (m, n) ;
+            gav.push_back (X) ;
+        } ;
+        if (x.t1 > x.t0) gathered (H, f.nscol - H, false) ;
+        if (f.ncb > 0)
+        {
+            if (assign_cb && assign_cb [fid])
+            {
+                Launch Lz {K_ZERO, 0, 0, S.zg.size (), 0, 0} ;
+                S.zg.push_back (ZeroGroup {f.cb, (i64) f.ncb, 0, 0}) ;
+                Lz.ng = 1 ; Lz.grid = (f.ncb + ZERO_COLS - 1) / ZERO_COLS ;
+                Lz.bytes = 8.0 * (double) f.ncb * (f.ncb + 1) / 2 ;
+                S.launches.push_back (Lz) ;
+            }
+            gathered (f.nscol, f.ncb, true) ;
+        }
+        gav_skipped += 2.0 * H * std::max (0.0, full - done) ;
+    }
+    void flush_gathered ()
+    {
+        if (gav.empty ()) return ;
+        Launch L {K_UPD_G, 0, 0, S.xg.size (), 0, 0} ;
+        i64 tiles = 0 ;
+        for (GatherGroup &X : gav)
+        {
+            GemmGroup &G = X.g ;
+            const i64 mine = place_region (G, SMALL, true, tiles) ;
+            G.nblk = (i32) mine ;
+            G.tile_start = X.tile_start = (i32) tiles ;
+            tiles += mine ;
+            const double elems = (double) G.n * (G.n + 1) / 2 + (double) (G.m - G.n) * G.n ;
+            L.flops += 2.0 * elems * G.k ;
+            L.aux = std::max (L.aux, (int) G.k) ;
+            L.bytes += (G.assign ? 8.0 : 16.0) * elems + 8.0 * ((double) G.m + G.n) * G.k ;
+            S.xg.push_back (X) ;
+        }
+        L.ng = (int) (S.xg.size () - L.goff) ;
+        L.grid = (int) tiles ;
+        L.half = tiles < w_half_max ? 1 : 0 ;
+        L.skipped = gav_skipped ;
+        S.launches.push_back (L) ;
+        gav.clear () ;
+        gav_skipped = 0 ;
     }
 
     // ---- exchange and windows of the shared fronts -----------------------------------------------------------------------
@@ -633,6 +726,7 @@ struct DenseScheduler
             if (ff) pf_done [x.q] = x.t0 ;
             if (!x.wide && is_shared (fid) && x.t1 > c0) { add_chunk_update (x, c0, ff) ; continue ; }
             if (x.wide && is_shared (fid) && !x.cb) { if (x.t1 > c0) add_wide_shared (x, c0, x.t1) ; continue ; }
+            if (x.cb && x.kc == 0 && x.kk == head_of (fid) && heads->gather) { add_head_gathered (x) ; continue ; }
             // the outer update of a distributed front: its in-front columns slab by slab on their owners
             if (x.cb && windowed (fid)) { if (x.t1 > c0) add_outer_slabs (f, fid, x.kc, x.kk, c0, x.t1) ; }
             else if (x.t1 > c0) add_update (f, fid, c0, x.kc, x.kk, f.nsrow - c0, x.t1 - c0, false, x.wide, ff) ;
@@ -674,9 +768,8 @@ struct DenseScheduler
         {
             const FrontD &f = fr [ids [q]] ;
             if (f.nscol <= i0 || (skip && (*skip) [q])) continue ;
-            int OBq = ob_of (f) ;
-            int o0 = (i0 / OBq) * OBq ;
-            int o1 = std::min (o0 + OBq, (int) f.nscol) ;
+            int o0, o1 ;
+            ob_bounds (q, i0, o0, o1) ;
             if (i0 + W >= o1)
             {
                 step.push_back (Upd {q, o0, o1 - o0, o1, f.nscol, true, true}) ;
@@ -736,9 +829,8 @@ struct DenseScheduler
         {
             const FrontD &f = fr [ids [q]] ;
             if (f.nscol <= i0) continue ;
-            int OBq = ob_of (f) ;
-            int o0 = (i0 / OBq) * OBq ;
-            int o1 = std::min (o0 + OBq, (int) f.nscol) ;
+            int o0, o1 ;
+            ob_bounds (q, i0, o0, o1) ;
             int b1 = std::min (i0 + SB, o1) ;
             int w = b1 - i0 ;
             int slot = (int) (S.cg.size () - Lc.goff) ;
@@ -767,9 +859,8 @@ struct DenseScheduler
         {
             const FrontD &f = fr [ids [q]] ;
             if (f.nscol <= i0) continue ;
-            int OBq = ob_of (f) ;
-            int o0 = (i0 / OBq) * OBq ;
-            int o1 = std::min (o0 + OBq, (int) f.nscol) ;
+            int o0, o1 ;
+            ob_bounds (q, i0, o0, o1) ;
             int b1 = std::min (i0 + SB, o1) ;
             int w = b1 - i0 ;
             int slot = (int) (S.dg.size () - Ld.goff) ;
@@ -835,9 +926,8 @@ struct DenseScheduler
         {
             const FrontD &f = fr [ids [q]] ;
             if (f.nscol < i0 + 2 * NB || is_shared (ids [q])) continue ;
-            int OBq = ob_of (f) ;
-            int o0 = (i0 / OBq) * OBq ;
-            int o1 = std::min (o0 + OBq, (int) f.nscol) ;
+            int o0, o1 ;
+            ob_bounds (q, i0, o0, o1) ;
             if (i0 + 2 * NB > o1) continue ;             // the next block belongs to the outer update
             int e = (i0 - o0) / NB + 1 ;
             if ((e & -e) != 1) continue ;               // p = 1 steps only
@@ -909,9 +999,9 @@ struct DenseScheduler
 
 void schedule_dense (const std::vector<FrontD> &fr, const i32 *ids, int nf,
     Schedule &S, int flags, const i32 *owner, const i32 *grp0, const i32 *grpn, int rank, int world,
-    const char *assign_cb, const i64 *win, const i32 *child, bool allow_half)
+    const char *assign_cb, const i64 *win, const i32 *child, bool allow_half, const HeadInfo *heads)
 {
-    DenseScheduler D (fr, ids, nf, S, flags, owner, grp0, grpn, rank, world, assign_cb, win, child, allow_half) ;
+    DenseScheduler D (fr, ids, nf, S, flags, owner, grp0, grpn, rank, world, assign_cb, win, child, allow_half, heads) ;
     D.run () ;
 }
 

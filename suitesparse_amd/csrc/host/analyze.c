@@ -797,6 +797,12 @@ cholmod_factor *cholmod_l_analyze_p2 (int for_whom, cholmod_sparse *A, SuiteSpar
     tt [3] = ssamd_now () ;
     if (ok) ok = cholmod_l_super_symbolic2 (for_whom, U, NULL, Parent, L, Common) ;
     tt [4] = ssamd_now () ;
+    /* where the relaxed fronts hold explicit zeros (numeric.c: ssamd_front_reach), for the engine's plan below; U is the
+     * pattern of P A P' with the factor's own permutation.  Nothing lost if it cannot be had: the plan is built without */
+    int64_t *reach_p = NULL ; int32_t *reach_first = NULL ;
+    const int ahead = ok && for_whom == CHOLMOD_ANALYZE_FOR_CHOLESKY && A->xtype == CHOLMOD_REAL && !Common->hip_lazy_plan ;
+    if (ahead && L->is_super && L->useGPU && Common->useGPU == 1 && Common->hip_world <= 1 && U)
+        ssamd_front_reach_alloc (U, L, &reach_p, &reach_first) ;
     if (timing)
         fprintf (stderr, "cholmod_l_analyze: ordering %.3f s, permute %.3f s, etree+colcounts+postorder(+re-permute) %.3f s, super_symbolic %.3f s\n",
             tt [1] - tt [0], tt [2] - tt [1], tt [3] - tt [2], tt [4] - tt [3]) ;
@@ -808,16 +814,18 @@ cholmod_factor *cholmod_l_analyze_p2 (int for_whom, cholmod_sparse *A, SuiteSpar
     if (Apk) cholmod_l_free_sparse (&Apk, Common) ;
     if (!ok)
     {
+        free (reach_p) ; free (reach_first) ;
         if (Common->status == CHOLMOD_OK) ERROR (CHOLMOD_OUT_OF_MEMORY, "analyze failed") ;
         cholmod_l_free_factor (&L, Common) ;
         return NULL ;
     }
     /* the engine's plan, as the reference cuts its device pools inside the analysis (cholmod_super_symbolic.c:243-327);
      * real matrices: a complex one is factorized through a twin factor that owns the plan (complex.c) */
-    if (for_whom == CHOLMOD_ANALYZE_FOR_CHOLESKY && A->xtype == CHOLMOD_REAL && !Common->hip_lazy_plan)
+    if (ahead)
     {
         double tp = ssamd_now () ;
-        ssamd_plan_ahead (L, Common) ;
+        ssamd_plan_ahead (L, Common, reach_p, reach_first) ;
+        free (reach_p) ; free (reach_first) ;
         if (timing) fprintf (stderr, "cholmod_l_analyze: engine plan (schedule, maps, HBM reservation) %.3f s%s\n", ssamd_now () - tp,
             L->hip_plan ? "" : " -- none built") ;
     }

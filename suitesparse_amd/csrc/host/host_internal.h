@@ -52,7 +52,9 @@ void ssamd_colcounts (Int n, const Int *Lp, const Int *Li, const Int *Parent, co
 int ssamd_nested_dissection (Int n, const Int *Ap, const Int *Ai, Int *Perm, cholmod_common *Common) ;
 int ssamd_resolve_use_gpu (cholmod_common *Common) ;
 int ssamd_ensure_plan (cholmod_factor *L, cholmod_common *Common) ;
-void ssamd_plan_ahead (cholmod_factor *L, cholmod_common *Common) ;
+void ssamd_plan_ahead (cholmod_factor *L, cholmod_common *Common, const int64_t *reach_p, const int32_t *reach_first) ;
+int64_t ssamd_front_reach (const cholmod_sparse *U, const cholmod_factor *L, int64_t *reach_p, int32_t *reach_first) ;
+void ssamd_front_reach_alloc (const cholmod_sparse *U, const cholmod_factor *L, int64_t **reach_p, int32_t **reach_first) ;
 
 /* complex.c: complex / zomplex input through the real embedding */
 int ssamd_complex_super_numeric (cholmod_sparse *A, double beta, cholmod_factor *L, cholmod_common *Common) ;

@@ -118,7 +118,10 @@ static int plan_flags_of (const cholmod_factor *L, const cholmod_common *Common)
     return flags ;
 }
 
-int ssamd_ensure_plan (cholmod_factor *L, cholmod_common *Common)
+static int ensure_plan_with (cholmod_factor *L, cholmod_common *Common, const int64_t *reach_p, const int32_t *reach_first) ;
+int ssamd_ensure_plan (cholmod_factor *L, cholmod_common *Common) { return ensure_plan_with (L, Common, NULL, NULL) ; }
+
+static int ensure_plan_with (cholmod_factor *L, cholmod_common *Common, const int64_t *reach_p, const int32_t *reach_first)
 {
     if (!ssamd_factor_has_cholesky_sizes (L))
     { ERROR (CHOLMOD_INVALID, "L was analysed for SPQR (no Cholesky sizes)") ; return FALSE ; }
@@ -134,8 +137,11 @@ int ssamd_ensure_plan (cholmod_factor *L, cholmod_common *Common)
     L->hip_plan_ahead = 0 ;
     if (L->hip_plan) return TRUE ;
     const double t_plan = omp_get_wtime () ;
-    cholmod_hip_plan *P = cholmod_hip_plan_create_dist ((int64_t) L->n, (int64_t) L->nsuper,
-        L->super, L->pi, L->px, L->s, flags, world > 1 ? Common->hip_rank : 0, world, &st) ;
+    cholmod_hip_plan *P = (reach_p && world == 1)
+        ? cholmod_hip_plan_create_reach ((int64_t) L->n, (int64_t) L->nsuper, L->super, L->pi, L->px, L->s, flags,
+            reach_p, reach_first, &st)
+        : cholmod_hip_plan_create_dist ((int64_t) L->n, (int64_t) L->nsuper,
+            L->super, L->pi, L->px, L->s, flags, world > 1 ? Common->hip_rank : 0, world, &st) ;
     Common->hip_plan_seconds = omp_get_wtime () - t_plan ;
     if (!P) return map_hip_status (st ? st : CHOLMOD_HIP_GPU_PROBLEM, Common, "HIP plan creation failed") ;
     /* (several ranks need an exchange: the Common->hip_allreduce callback, or the
@@ -150,14 +156,113 @@ int ssamd_ensure_plan (cholmod_factor *L, cholmod_common *Common)
 /* The plan at the end of cholmod_l_analyze (Common->hip_lazy_plan == 0; one GPU -- the ranks of a multi-GPU run attach their
  * exchange to the plan after cholmod_l_hip_prepare).  Not an error of the analysis when it cannot be built: L stays without
  * a plan, the first factorization tries again and reports. */
-void ssamd_plan_ahead (cholmod_factor *L, cholmod_common *Common)
+/* ---- where the relaxed fronts hold explicit zeros ------------------------------------------------------------------------
+ * For every supernode s of at least REACH_MIN_COLS columns: reach_first [reach_p [s] + p] = the first column of s (counted
+ * from its first column) whose pattern holds the row at position p of its row list, INT32_MAX if none does.  Column k of L
+ * gets its pattern from A's column k, from the contribution blocks of the children whose first row past their own columns
+ * is k, and from the earlier columns of its own supernode; so the rows the columns [0, H) of s reach are the rows of A's
+ * pattern in those columns and the contribution-block rows of the children attached to them -- the prefix union is closed
+ * under the third source.  The children's row lists are relaxed (a superset of their exact patterns), so the reach is
+ * never smaller than the exact one.  U: the upper pattern of P A P' with the factor's own permutation (L->Perm).
+ * Returns the length of reach_first (reach_first == NULL: only reach_p is filled), -1 on failure. */
+#define REACH_MIN_COLS 512
+int64_t ssamd_front_reach (const cholmod_sparse *U, const cholmod_factor *L, int64_t *reach_p, int32_t *reach_first)
+{
+    const Int nsuper = (Int) L->nsuper, n = (Int) L->n ;
+    const Int *super = L->super, *pi = L->pi, *Ls = L->s ;
+    if (!U || !L->is_super || (Int) U->ncol != n) return -1 ;
+    reach_p [0] = 0 ;
+    for (Int s = 0 ; s < nsuper ; s++)
+    {
+        const Int nscol = super [s + 1] - super [s], nsrow = pi [s + 1] - pi [s] ;
+        reach_p [s + 1] = reach_p [s] + (nscol >= REACH_MIN_COLS ? nsrow : 0) ;
+    }
+    if (!reach_first || reach_p [nsuper] == 0) return reach_p [nsuper] ;
+    Int *smap = malloc ((size_t) (n > 0 ? n : 1) * sizeof (Int)) ;
+    if (!smap) return -1 ;
+    for (Int s = 0 ; s < nsuper ; s++)
+        for (Int k = super [s] ; k < super [s + 1] ; k++) smap [k] = s ;
+    for (int64_t q = 0 ; q < reach_p [nsuper] ; q++) reach_first [q] = INT32_MAX ;
+    for (Int s = 0 ; s < nsuper ; s++)
+        if (reach_p [s + 1] > reach_p [s])
+            for (Int p = 0 ; p < super [s + 1] - super [s] ; p++) reach_first [reach_p [s] + p] = (int32_t) p ;
+    /* position of row i in the row list of s (sorted), or -1 */
+    #define ROW_POS(s, i, pos) do { Int lo_ = pi [s], hi_ = pi [s + 1] ; \
+        while (lo_ < hi_) { Int mid_ = (lo_ + hi_) >> 1 ; if (Ls [mid_] < (i)) lo_ = mid_ + 1 ; else hi_ = mid_ ; } \
+        (pos) = (lo_ < pi [s + 1] && Ls [lo_] == (i)) ? lo_ - pi [s] : -1 ; } while (0)
+    /* A: column i of U holds the rows k <= i, i.e. column k of the lower part holds row i */
+    const Int *Up = U->p, *Ui = U->i, *Unz = U->nz ;
+    for (Int i = 0 ; i < n ; i++)
+    {
+        const Int pend = U->packed ? Up [i + 1] : Up [i] + Unz [i] ;
+        for (Int q = Up [i] ; q < pend ; q++)
+        {
+            const Int k = Ui [q], s = (k < i) ? smap [k] : -1 ;
+            if (s < 0 || reach_p [s + 1] == reach_p [s]) continue ;
+            Int pos ;
+            ROW_POS (s, i, pos) ;
+            int32_t *fp = reach_first + reach_p [s] + pos ;
+            if (pos >= 0 && *fp > (int32_t) (k - super [s])) *fp = (int32_t) (k - super [s]) ;
+        }
+    }
+    /* children: their contribution-block rows, from the column of the parent where the block begins */
+    for (Int c = 0 ; c < nsuper ; c++)
+    {
+        const Int nscol = super [c + 1] - super [c], p0 = pi [c] + nscol ;
+        if (p0 >= pi [c + 1]) continue ;
+        const Int s = smap [Ls [p0]] ;
+        if (reach_p [s + 1] == reach_p [s]) continue ;
+        const int32_t f = (int32_t) (Ls [p0] - super [s]) ;
+        Int pos = 0 ;
+        for (Int q = p0 ; q < pi [c + 1] ; q++)
+        {
+            while (pi [s] + pos < pi [s + 1] && Ls [pi [s] + pos] < Ls [q]) pos++ ;     /* (both lists sorted) */
+            if (pi [s] + pos < pi [s + 1] && Ls [pi [s] + pos] == Ls [q] && reach_first [reach_p [s] + pos] > f)
+                reach_first [reach_p [s] + pos] = f ;
+        }
+    }
+    #undef ROW_POS
+    free (smap) ;
+    return reach_p [nsuper] ;
+}
+
+void ssamd_front_reach_alloc (const cholmod_sparse *U, const cholmod_factor *L, int64_t **reach_p, int32_t **reach_first)
+{
+    *reach_p = malloc (((size_t) L->nsuper + 1) * sizeof (int64_t)) ;
+    *reach_first = NULL ;
+    int64_t len = *reach_p ? ssamd_front_reach (U, L, *reach_p, NULL) : -1 ;
+    if (len > 0) *reach_first = malloc ((size_t) len * sizeof (int32_t)) ;
+    if (len > 0 && *reach_first && ssamd_front_reach (U, L, *reach_p, *reach_first) == len) return ;
+    free (*reach_p) ; free (*reach_first) ;
+    *reach_p = NULL ; *reach_first = NULL ;
+}
+
+/* the same for a caller's A and an analysed L (tests, tools): A lower or upper stored, real or pattern */
+int64_t cholmod_l_hip_front_reach (cholmod_sparse *A, cholmod_factor *L, int64_t *reach_p, int32_t *reach_first,
+    cholmod_common *Common)
+{
+    if (!A || !L || !reach_p || !L->is_super || !L->Perm || A->stype == 0 || A->nrow != L->n) return -1 ;
+    cholmod_sparse *U = NULL, *Lw = NULL ;
+    if (A->stype < 0) U = cholmod_l_ptranspose (A, 0, L->Perm, NULL, 0, Common) ;
+    else
+    {
+        Lw = cholmod_l_ptranspose (A, 0, L->Perm, NULL, 0, Common) ;
+        if (Lw) U = cholmod_l_ptranspose (Lw, 0, NULL, NULL, 0, Common) ;
+    }
+    const int64_t len = U ? ssamd_front_reach (U, L, reach_p, reach_first) : -1 ;
+    cholmod_l_free_sparse (&U, Common) ;
+    cholmod_l_free_sparse (&Lw, Common) ;
+    return len ;
+}
+
+void ssamd_plan_ahead (cholmod_factor *L, cholmod_common *Common, const int64_t *reach_p, const int32_t *reach_first)
 {
     if (!L || !L->is_super || !L->useGPU || L->hip_plan || Common->useGPU != 1) return ;
     if (Common->hip_world > 1 || Common->hip_allreduce) return ;
     if (!ssamd_factor_has_cholesky_sizes (L) || !cholmod_hip_probe ()) return ;
     const int st = Common->status, tc = Common->try_catch ;
     Common->try_catch = TRUE ;
-    if (ssamd_ensure_plan (L, Common)) L->hip_plan_ahead = plan_flags_of (L, Common) + 1 ;
+    if (ensure_plan_with (L, Common, reach_p, reach_first)) L->hip_plan_ahead = plan_flags_of (L, Common) + 1 ;
     Common->try_catch = tc ; Common->status = st ;
 }
 
