@@ -251,7 +251,7 @@ typedef struct cholmod_factor_struct
     void *cx_twin ;
     /* pattern of the last matrix cholmod_l_factorize handed to the engine (hash of its
      * p / i arrays, its nnz): a call with the same pattern only refreshes the values of
-     * the resident matrix (cholmod_hip_refresh_values) */
+     * the resident matrix (cholmod_hip_values_begin / _push_chunk) */
     uint64_t hip_apat_hash ;
     size_t hip_apat_nnz ;
     int hip_apat_valid ;

@@ -214,29 +214,22 @@ int cholmod_hip_factorize_resident (cholmod_hip_plan *plan, double beta,
  * (cholmod_l_factorize called again with the same pattern: the common case of a
  * nonlinear or time-stepping loop).  cholmod_hip_set_value_map hands over, once per
  * upload, where every entry of the resident packed S came from in the caller's value
- * array: src [q] in [0, nvalues).  cholmod_hip_refresh_values then copies the caller's
- * nvalues doubles to the device and gathers Sx [q] = values [src [q]] there -- no
- * host-side permutation, no pattern upload, the assembly map stays valid.
- * Both return CHOLMOD_HIP_INVALID without a resident packed S of snz entries. */
+ * array: src [q] in [0, nvalues); CHOLMOD_HIP_INVALID without a resident packed S of snz
+ * entries.  A later call then sends the values only -- no host-side permutation, no
+ * pattern upload, the assembly map stays valid -- as a pipeline the caller drives:
+ * cholmod_hip_values_begin hands out a PINNED staging buffer owned by the plan and the
+ * gather index: *buffer [k] must receive values [index [k]] for k < *count, or, with
+ * *index == NULL (no batch order: several ranks, CHOLMOD_HIP_VALUES_IN_BATCH_ORDER=0, ...),
+ * values [k] for k < *count = nvalues; it enqueues the clearing of L at once.  The caller
+ * fills the buffer chunk by chunk (*chunk_len positions, a multiple of 32768) and calls
+ * cholmod_hip_values_push_chunk (c) for c = 0, 1, ... in order as each chunk is complete --
+ * an asynchronous DMA -- or (-1) to cancel; cholmod_hip_factorize_resident, called once
+ * after begin from any thread, waits for the chunks it needs (engine.hip has the protocol)
+ * and returns an error after a cancel. */
 int cholmod_hip_set_value_map (cholmod_hip_plan *plan, const int64_t *src, int64_t snz,
     int64_t nvalues) ;
-int cholmod_hip_refresh_values (cholmod_hip_plan *plan, const double *values, int64_t nvalues) ;
-/* The same upload as a pipeline the caller drives (round 5): cholmod_hip_values_staging hands out a PINNED host buffer of
- * nvalues doubles owned by the plan; the caller fills it chunk by chunk (with its own threads) and calls
- * cholmod_hip_values_push (offset, count) after every chunk -- an asynchronous DMA, no host wait; cholmod_hip_values_commit
- * (plan, 1) then enqueues the gather into the resident S and an event the ASSEMBLY of the next cholmod_hip_factorize_resident
- * waits for (the clearing of L runs beside the upload); commit = 0 abandons what was pushed (the pattern changed after all)
- * and waits until nothing is in flight.  The caller's own array may be reused as soon as it has been copied out. */
-int cholmod_hip_values_staging (cholmod_hip_plan *plan, double **host_buffer, int64_t *nvalues) ;
-int cholmod_hip_values_push (cholmod_hip_plan *plan, int64_t offset, int64_t count) ;
-int cholmod_hip_values_commit (cholmod_hip_plan *plan, int commit) ;
-/* Round 6: the same upload in the order the factorization needs the values, chunk by chunk, so that a batch of fronts
- * waits for its own entries only (cholmod_l_factorize drives it from three kinds of host threads; engine.hip has the
- * protocol).  cholmod_hip_values_gather_index: *index = where staged position k comes from in the caller's value array, or
- * NULL when this plan has no batch order (several ranks, no assembly map yet) -- then staging / push / commit above apply;
- * *count = staged positions (the entries of the resident S), *chunk_len = positions per chunk. */
-int cholmod_hip_values_gather_index (cholmod_hip_plan *plan, const int64_t **index, int64_t *chunk_len, int64_t *count) ;
-int cholmod_hip_values_begin (cholmod_hip_plan *plan) ;
+int cholmod_hip_values_begin (cholmod_hip_plan *plan, double **buffer, const int64_t **index,
+    int64_t *count, int64_t *chunk_len) ;
 int cholmod_hip_values_push_chunk (cholmod_hip_plan *plan, int64_t chunk) ;
 
 /* Copy the device-resident packed Lx (xsize doubles) to the host. */

@@ -57,7 +57,6 @@ static void free_device (cholmod_hip_plan *P)
 {
     if (P->prog_dev) { (void) hipHostFree (P->prog_dev) ; P->prog_dev = nullptr ; }
     if (P->h_vals) { (void) hipHostFree (P->h_vals) ; P->h_vals = nullptr ; }
-    if (P->values_ev) { (void) hipEventDestroy (P->values_ev) ; P->values_ev = nullptr ; }
     for (auto e : P->chunk_ev) (void) hipEventDestroy (e) ;
     P->chunk_ev.clear () ;
     if (P->d_vorder) { (void) hipFree (P->d_vorder) ; P->d_vorder = nullptr ; }
@@ -547,6 +546,18 @@ static void exchange_volume (const cholmod_hip_plan *P, double *S)
     }
 }
 
+/* host side: until the caller has pushed chunk c (cholmod_hip_values_push_chunk); an error if it cancelled */
+static int wait_pushed (cholmod_hip_plan *P, long c)
+{
+    for (long spin = 0 ; ; spin++)
+    {
+        const long have = P->chunks_pushed.load (std::memory_order_acquire) ;
+        if (have < 0) return CHOLMOD_HIP_GPU_PROBLEM ;
+        if (have > c) return CHOLMOD_HIP_OK ;
+        if ((spin & 1023) == 1023) std::this_thread::yield () ;
+    }
+}
+
 // Run the numeric factorization on the resident S.  Leaves Lx on the device.
 /* the chunks 0 .. need-1 into S and L, on the main stream, as soon as each has been pushed and copied */
 static int apply_value_chunks (cholmod_hip_plan *P, long need)
@@ -554,13 +565,8 @@ static int apply_value_chunks (cholmod_hip_plan *P, long need)
     while (P->chunks_applied < need)
     {
         const long c = P->chunks_applied ;
-        for (long spin = 0 ; ; spin++)
-        {
-            const long have = P->chunks_pushed.load (std::memory_order_acquire) ;
-            if (have < 0) return CHOLMOD_HIP_GPU_PROBLEM ;
-            if (have > c) break ;
-            if ((spin & 1023) == 1023) std::this_thread::yield () ;
-        }
+        const int rw = wait_pushed (P, c) ;
+        if (rw != CHOLMOD_HIP_OK) return rw ;
         HIPCHK (hipStreamWaitEvent (P->stream, P->chunk_ev [c], 0)) ;
         const i64 k0 = c * P->chunk_len, k1 = std::min<i64> (k0 + P->chunk_len, P->s_cur_nz) ;
         hipLaunchKernelGGL (k_values_chunk, dim3 ((unsigned) ((k1 - k0 + 255) / 256)), dim3 (256), 0, P->stream,
@@ -640,30 +646,29 @@ static int run_factorize (cholmod_hip_plan *P, double beta, int quick, i64 *mino
     int poisoned = CHOLMOD_HIP_OK ;
     bool building_map = false ;
     if (prof) HIPCHK (hipEventRecord (P->evpool [0], st)) ;
-    if (!P->prologue_done)
+    const bool begun = P->values_begun, chunked = begun && P->values_in_batch_order ;
+    P->values_begun = false ;
+    if (!begun)
     {
         const int rp = factorize_prologue (P) ;
         if (rp != CHOLMOD_HIP_OK) return rp ;
     }
-    P->prologue_done = false ;
-    const bool chunked = P->values_chunked ;
-    P->values_chunked = false ;
+    else if (!chunked && P->nchunks > 0)
+    {
+        // (cholmod_hip_values_begin in S order: the push of the last chunk gathers the new values into S on the exchange
+        // stream; the clearing of L ran beside their upload, the assembly is the first to read them)
+        const int rw = wait_pushed (P, P->nchunks - 1) ;
+        if (rw != CHOLMOD_HIP_OK) return rw ;
+        HIPCHK (hipStreamWaitEvent (st, P->chunk_ev [P->nchunks - 1], 0)) ;
+    }
     if (chunked)
     {
-        // (cholmod_hip_values_begin: the values arrive chunk by chunk in batch order; the diagonal shift first, every chunk
-        // is added into the cleared L right before the first launch of the first batch that needs it)
+        // (in batch order: the diagonal shift first, every chunk is added into the cleared L right before the first launch
+        // of the first batch that needs it)
         if (beta != 0.0 && P->n > 0)
             hipLaunchKernelGGL (k_add_beta<false>, dim3 ((unsigned) ((P->n + 255) / 256)), dim3 (256), 0, st,
                 P->n, P->d_supermap, P->d_fr, P->d_Lx, beta) ;
     }
-    if (!chunked && P->values_pending)
-    {
-        // (cholmod_hip_values_commit: the new values of S arrive on the exchange stream; everything above -- the clearing of
-        // L -- ran beside their upload, the assembly is the first to read them)
-        HIPCHK (hipStreamWaitEvent (st, P->values_ev, 0)) ;
-        P->values_pending = false ;
-    }
-    if (chunked) { }
     else if (P->n > 0 && P->amap_valid)
     {
         // the resident S was assembled before: stream it through its map
@@ -1437,7 +1442,7 @@ int cholmod_hip_upload_matrix (cholmod_hip_plan *P, const int64_t *Sp, const int
     P->amap_valid = false ;         // a new pattern may have come with the new values
     P->s_cur_nz = nz ;
     P->vsrc_nz = 0 ;                // ... and the value map of the previous one is void
-    P->h_vgather.clear () ; P->values_chunked = false ;
+    P->h_vgather.clear () ; P->nchunks = 0 ;
     if (!Snz && P->world == 1) P->h_Sp.assign (Sp, Sp + n + 1) ; else P->h_Sp.clear () ;
     return CHOLMOD_HIP_OK ;
 }
@@ -1456,7 +1461,7 @@ int cholmod_hip_set_value_map (cholmod_hip_plan *P, const int64_t *src, int64_t 
     // first -- a thin front's entries by its own launch (the thin-front kernels read their columns of S themselves), a
     // generic front's by the first launch of its batch behind the thin ones (k_values_chunk has then put them into L) --
     // and by source position inside such a class.  One rank, packed S.
-    P->h_vgather.clear () ; P->batch_entries_end.clear () ; P->launch_need_chunks.clear () ;
+    P->h_vgather.clear () ; P->launch_need_chunks.clear () ;
     if (P->d_vorder) { (void) hipFree (P->d_vorder) ; P->d_vorder = nullptr ; }
     static const bool chunked_off = getenv ("CHOLMOD_HIP_VALUES_IN_BATCH_ORDER") && !strcmp (getenv ("CHOLMOD_HIP_VALUES_IN_BATCH_ORDER"), "0") ;
     if (!chunked_off && P->world == 1 && !(P->flags & CHOLMOD_HIP_CX_STORAGE) && (i64) P->h_Sp.size () == P->n + 1 && snz > 0 && snz <= nvalues
@@ -1532,89 +1537,31 @@ int cholmod_hip_set_value_map (cholmod_hip_plan *P, const int64_t *src, int64_t 
             }
             HIPCHK (hipMalloc ((void **) &P->d_vorder, (size_t) snz * sizeof (i64))) ;
             HIPCHK (hipMemcpy (P->d_vorder, order.data (), (size_t) snz * sizeof (i64), hipMemcpyHostToDevice)) ;
-            P->nchunks = (long) ((snz + P->chunk_len - 1) / P->chunk_len) ;
             // chunks a launch needs = those that hold the entries of every class up to its own
-            P->launch_need_chunks.assign (nl + 1, (i32) P->nchunks) ;
+            P->launch_need_chunks.assign (nl + 1, (i32) ((snz + P->chunk_len - 1) / P->chunk_len)) ;
             for (size_t q = 0 ; q < nl ; q++) P->launch_need_chunks [q] = (i32) ((cnt [q + 1] + P->chunk_len - 1) / P->chunk_len) ;
-            while ((long) P->chunk_ev.size () < P->nchunks)
-            {
-                hipEvent_t e ; HIPCHK (hipEventCreateWithFlags (&e, hipEventDisableTiming)) ; P->chunk_ev.push_back (e) ;
-            }
         }
     }
     return CHOLMOD_HIP_OK ;
 }
 
-/* Round 6 -- the value upload in the order the factorization needs it.  cholmod_hip_values_gather_index: where staged
- * position k comes from in the caller's value array (NULL: no batch order for this plan -- use staging / push / commit as
- * before) and the chunk length.  The caller then runs three roles on threads of its own:
- *   * cholmod_hip_values_begin (plan): the clearing of L is enqueued at once (it runs beside the upload), the chunk
- *     counters are reset; then cholmod_hip_factorize_resident, whose launch loop waits -- host side for the push, device
- *     side for the copy -- only for the chunks the next batch needs, applies them (k_values_chunk) and goes on;
- *   * staging: host_buffer [k] = values [index [k]], chunk by chunk;
- *   * cholmod_hip_values_push_chunk (plan, c) for c = 0, 1, ... as chunks are staged (one thread, in order);
- *     cholmod_hip_values_push_chunk (plan, -1) if the staging failed: the waiting factorization returns an error.
- * Nothing of this touches the resident S before the factorization applies it, chunk by chunk. */
-int cholmod_hip_values_gather_index (cholmod_hip_plan *P, const int64_t **index, int64_t *chunk_len, int64_t *count)
+/* The value upload of a call with the pattern of the resident S (cholmod_l_factorize), driven by the caller's threads:
+ *   * cholmod_hip_values_begin: the plan's pinned staging buffer, and where staged position k comes from in the caller's
+ *     value array -- in batch order (the entries of S sorted by the launch that first needs them, set_value_map above) --
+ *     or NULL: in S order, the caller's array as it is.  The clearing of L is enqueued at once (it runs beside the
+ *     upload), the chunk counters are reset;
+ *   * cholmod_hip_factorize_resident follows.  In batch order its launch loop waits -- host side for the push, device side
+ *     for the copy -- only for the chunks the next batch needs, applies them (k_values_chunk) and goes on; in S order
+ *     every launch needs every value: it waits for the last push, whose gather into S the assembly waits for on the device;
+ *   * cholmod_hip_values_push_chunk (plan, c) for c = 0, 1, ... as chunks are staged (one thread, in order; a DMA on the
+ *     exchange stream, no host wait); (plan, -1) cancels: the waiting factorization returns an error.
+ * Nothing of this touches the resident S before the factorization's turn. */
+int cholmod_hip_values_begin (cholmod_hip_plan *P, double **buffer, const int64_t **index, int64_t *count, int64_t *chunk_len)
 {
-    if (!P || !index || !chunk_len || !count) return CHOLMOD_HIP_INVALID ;
-    const bool ok = !P->h_vgather.empty () && (i64) P->h_vgather.size () == P->s_cur_nz && P->vsrc_nz == P->s_cur_nz
-        && P->amap_valid && P->d_vorder && P->launch_need_chunks.size () == P->sch.launches.size () + 1 ;
-    *index = ok ? P->h_vgather.data () : nullptr ;
-    *chunk_len = P->chunk_len ;
-    *count = P->s_cur_nz ;
-    return CHOLMOD_HIP_OK ;
-}
-
-int cholmod_hip_values_begin (cholmod_hip_plan *P)
-{
-    if (!P || !P->h_vals || P->h_vgather.empty () || !P->amap_valid) return CHOLMOD_HIP_INVALID ;
-    P->chunks_pushed.store (0) ;
-    P->chunks_applied = 0 ;
-    P->values_chunked = true ;
-    P->values_pending = false ;
-    const int rc = factorize_prologue (P) ;
-    if (rc != CHOLMOD_HIP_OK) { P->values_chunked = false ; return rc ; }
-    P->prologue_done = true ;
-    return CHOLMOD_HIP_OK ;
-}
-
-int cholmod_hip_values_push_chunk (cholmod_hip_plan *P, int64_t c)
-{
-    if (!P || !P->h_vals) return CHOLMOD_HIP_INVALID ;
-    if (c < 0 || c >= P->nchunks) { P->chunks_pushed.store (-1) ; return CHOLMOD_HIP_INVALID ; }
-    const i64 k0 = c * P->chunk_len, k1 = std::min<i64> (k0 + P->chunk_len, P->s_cur_nz) ;
-    if (hipMemcpyAsync (P->d_vals + k0, P->h_vals + k0, (size_t) (k1 - k0) * sizeof (double), hipMemcpyHostToDevice, P->stream2) != hipSuccess
-        || hipEventRecord (P->chunk_ev [c], P->stream2) != hipSuccess)
-    {
-        (void) hipGetLastError () ;
-        P->chunks_pushed.store (-1) ;
-        return CHOLMOD_HIP_GPU_PROBLEM ;
-    }
-    P->chunks_pushed.store ((long) c + 1, std::memory_order_release) ;
-    return CHOLMOD_HIP_OK ;
-}
-
-int cholmod_hip_refresh_values (cholmod_hip_plan *P, const double *values, int64_t nvalues)
-{
-    if (!P || P->host_only || !values || !P->d_vsrc || P->vsrc_nz != P->s_cur_nz || nvalues != P->vals_n)
+    if (!P || P->host_only || !buffer || !index || !count || !chunk_len || !P->d_vsrc || P->vsrc_nz != P->s_cur_nz)
         return CHOLMOD_HIP_INVALID ;
-    if (nvalues) HIPCHK (hipMemcpyAsync (P->d_vals, values, nvalues * sizeof (double), hipMemcpyHostToDevice, P->stream)) ;
-    if (P->vsrc_nz)
-        hipLaunchKernelGGL (k_gather_values, dim3 ((unsigned) ((P->vsrc_nz + 255) / 256)), dim3 (256), 0, P->stream,
-            P->vsrc_nz, P->d_vsrc, P->d_vals, P->d_Sx) ;
-    HIPCHK (hipStreamSynchronize (P->stream)) ;     // the caller may reuse `values` at once
-    return CHOLMOD_HIP_OK ;
-}
-
-/* The same, pipelined (round 5: the API step of the small configurations is a third H2D + host work): the caller copies
- * A->x chunk by chunk into a pinned staging buffer of the plan (its own threads, cholmod_hip_values_staging) and pushes every
- * chunk as soon as it is filled (cholmod_hip_values_push: DMA on the exchange stream, no host wait); while the last chunks
- * travel it does what else it has to do (the pattern hash), then commits (gather into the resident S, an event the next
- * factorization's ASSEMBLY waits for -- its clearing of L, 1 to 10 GB of memset, runs beside the upload) or cancels. */
-int cholmod_hip_values_staging (cholmod_hip_plan *P, double **host_buffer, int64_t *nvalues)
-{
-    if (!P || P->host_only || !host_buffer || !nvalues || !P->d_vsrc || P->vsrc_nz != P->s_cur_nz) return CHOLMOD_HIP_INVALID ;
+    const bool batch = !P->h_vgather.empty () && (i64) P->h_vgather.size () == P->s_cur_nz && P->amap_valid && P->d_vorder
+        && P->launch_need_chunks.size () == P->sch.launches.size () + 1 ;
     if (!P->h_vals || P->h_vals_n != P->vals_n)
     {
         if (P->h_vals) { (void) hipHostFree (P->h_vals) ; P->h_vals = nullptr ; }
@@ -1626,35 +1573,43 @@ int cholmod_hip_values_staging (cholmod_hip_plan *P, double **host_buffer, int64
         }
         P->h_vals_n = P->vals_n ;
     }
-    if (!P->values_ev) HIPCHK (hipEventCreateWithFlags (&P->values_ev, hipEventDisableTiming)) ;
-    *host_buffer = P->h_vals ; *nvalues = P->vals_n ;
+    const i64 staged = batch ? P->s_cur_nz : P->vals_n ;
+    P->nchunks = (long) ((staged + P->chunk_len - 1) / P->chunk_len) ;
+    while ((long) P->chunk_ev.size () < P->nchunks)
+    {
+        hipEvent_t e ; HIPCHK (hipEventCreateWithFlags (&e, hipEventDisableTiming)) ; P->chunk_ev.push_back (e) ;
+    }
+    const int rc = factorize_prologue (P) ;
+    if (rc != CHOLMOD_HIP_OK) return rc ;
+    P->chunks_pushed.store (0) ;
+    P->chunks_applied = 0 ;
+    P->values_begun = true ;
+    P->values_in_batch_order = batch ;
+    *buffer = P->h_vals ; *index = batch ? P->h_vgather.data () : nullptr ;
+    *count = staged ; *chunk_len = P->chunk_len ;
     return CHOLMOD_HIP_OK ;
 }
 
-int cholmod_hip_values_push (cholmod_hip_plan *P, int64_t offset, int64_t count)
-{
-    if (!P || !P->h_vals || offset < 0 || count < 0 || offset + count > P->vals_n) return CHOLMOD_HIP_INVALID ;
-    if (count) HIPCHK (hipMemcpyAsync (P->d_vals + offset, P->h_vals + offset, (size_t) count * sizeof (double), hipMemcpyHostToDevice, P->stream2)) ;
-    return CHOLMOD_HIP_OK ;
-}
-
-int cholmod_hip_values_commit (cholmod_hip_plan *P, int commit)
+int cholmod_hip_values_push_chunk (cholmod_hip_plan *P, int64_t c)
 {
     if (!P || !P->h_vals) return CHOLMOD_HIP_INVALID ;
-    if (!commit)
+    if (c < 0 || c >= P->nchunks) { P->chunks_pushed.store (-1) ; return CHOLMOD_HIP_INVALID ; }
+    const bool s_order = !P->values_in_batch_order ;
+    const i64 k0 = c * P->chunk_len, k1 = std::min<i64> (k0 + P->chunk_len, s_order ? P->vals_n : P->s_cur_nz) ;
+    bool ok = hipMemcpyAsync (P->d_vals + k0, P->h_vals + k0, (size_t) (k1 - k0) * sizeof (double), hipMemcpyHostToDevice, P->stream2) == hipSuccess ;
+    if (ok && s_order && c == P->nchunks - 1 && P->vsrc_nz > 0)
     {
-        // (the pattern turned out to be another one: nothing of the staged values may reach the resident S, and whoever
-        // rewrites S next must not meet a copy in flight)
-        HIPCHK (hipStreamSynchronize (P->stream2)) ;
-        P->values_pending = false ;
-        return CHOLMOD_HIP_OK ;
-    }
-    if (P->vsrc_nz)
         hipLaunchKernelGGL (k_gather_values, dim3 ((unsigned) ((P->vsrc_nz + 255) / 256)), dim3 (256), 0, P->stream2,
             P->vsrc_nz, P->d_vsrc, P->d_vals, P->d_Sx) ;
-    HIPCHK (hipGetLastError ()) ;
-    HIPCHK (hipEventRecord (P->values_ev, P->stream2)) ;
-    P->values_pending = true ;
+        ok = hipGetLastError () == hipSuccess ;
+    }
+    if (!ok || hipEventRecord (P->chunk_ev [c], P->stream2) != hipSuccess)
+    {
+        (void) hipGetLastError () ;
+        P->chunks_pushed.store (-1) ;
+        return CHOLMOD_HIP_GPU_PROBLEM ;
+    }
+    P->chunks_pushed.store ((long) c + 1, std::memory_order_release) ;
     return CHOLMOD_HIP_OK ;
 }
 

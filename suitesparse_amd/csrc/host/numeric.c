@@ -299,16 +299,21 @@ static int back_to_symbolic (cholmod_factor *L)
     return FALSE ;
 }
 
+/* the device copy of L is void: a numeric L keeps the values it has on the host, if it has them (the reference leaves the old
+ * values of a numeric L in place); otherwise L is symbolic again -- never a "numeric" L whose device factor is a zeroed,
+ * partial or foreign one */
+static void forget_device_factor (cholmod_factor *L)
+{
+    if (L->x && L->hip_host_valid) L->hip_on_device = FALSE ;
+    else back_to_symbolic (L) ;
+}
+
 static int finish_numeric (int rc, int64_t minor, cholmod_factor *L, cholmod_common *Common)
 {
     const int was_symbolic = (L->xtype == CHOLMOD_PATTERN && !L->x) ;
     if (rc < 0)
     {
-        /* the device copy is void whatever L was on entry (run_factorize clears it first): a numeric L keeps the values
-         * it has on the host, if it has them (the reference leaves the old values of a numeric L in place); otherwise L is
-         * symbolic again -- never a "numeric" L whose device factor is a zeroed or partial one */
-        if (was_symbolic || !(L->x && L->hip_host_valid)) back_to_symbolic (L) ;
-        else L->hip_on_device = FALSE ;
+        forget_device_factor (L) ;         /* (whatever L was on entry: run_factorize clears it first) */
         return map_hip_status (rc, Common, "HIP factorization failed") ;
     }
     L->xtype = CHOLMOD_REAL ;
@@ -465,8 +470,6 @@ static double api_now (void)
     return (double) ts.tv_sec + 1e-9 * (double) ts.tv_nsec ;
 }
 
-/* 64-bit hash of a packed pattern (dimensions, stype, p, i): the key under which the
- * engine's value map of a matrix is remembered */
 /* Two independent 64-bit fingerprints of the pattern (p and i arrays): the values-only fast
  * path of cholmod_l_factorize trusts them as proof that the resident S and its value map still
  * fit A.  Each is a sum of position-keyed, avalanche-mixed words (order-independent, hence
@@ -487,73 +490,165 @@ static int api_threads (void)
 
 typedef struct { uint64_t hp, gp, hi, gi ; } pat_sums ;
 
-/* the column pointers j0 .. j1-1 / the row indices p0 .. p1-1 into the four sums (order-independent: any split will do) */
-static void pattern_hash_p (const Int *Ap, Int j0, Int j1, pat_sums *S)
+/* the pattern is hashed in pieces of HASH_PIECE entries: the ncol + 1 column pointers first, then the row indices */
+#define HASH_PIECE ((int64_t) 1 << 16)
+
+static int64_t hash_pieces (const cholmod_sparse *A)
 {
-    uint64_t hp = 0, gp = 0 ;
-    for (Int j = j0 ; j < j1 ; j++)
-    {
-        uint64_t x = (uint64_t) Ap [j] + 0x9E3779B97F4A7C15ull * (uint64_t) (j + 1) ;
-        x ^= x >> 30 ; x *= 0xbf58476d1ce4e5b9ull ; x ^= x >> 27 ; x *= 0x94d049bb133111ebull ; x ^= x >> 31 ;
-        hp += x ;
-        uint64_t y = ((uint64_t) Ap [j] ^ 0xA24BAED4963EE407ull) * (2 * (uint64_t) j + 0x632BE59BD9B4E019ull) ;
-        y ^= y >> 33 ; y *= 0xff51afd7ed558ccdull ; y ^= y >> 33 ; y *= 0xc4ceb9fe1a85ec53ull ; y ^= y >> 33 ;
-        gp += y ;
-    }
-    S->hp += hp ; S->gp += gp ;
+    const int64_t ncol = (int64_t) A->ncol, nz = ((Int *) A->p) [ncol] ;
+    return (ncol + HASH_PIECE) / HASH_PIECE + (nz + HASH_PIECE - 1) / HASH_PIECE ;
 }
 
-static void pattern_hash_i (const Int *Ai, Int p0, Int p1, pat_sums *S)
+/* piece k into the four sums (order-independent: any thread may take any piece) */
+static void hash_piece (const cholmod_sparse *A, int64_t k, pat_sums *S)
 {
-    uint64_t hi = 0, gi = 0 ;
-    for (Int p = p0 ; p < p1 ; p++)
+    const Int *Ap = A->p, *Ai = A->i ;
+    const int64_t ncol = (int64_t) A->ncol, nz = Ap [ncol], nhp = (ncol + HASH_PIECE) / HASH_PIECE ;
+    uint64_t h = 0, g = 0 ;
+    if (k < nhp)
     {
-        uint64_t x = (uint64_t) Ai [p] + 0xD1B54A32D192ED03ull * (uint64_t) (p + 1) ;
-        x ^= x >> 30 ; x *= 0xbf58476d1ce4e5b9ull ; x ^= x >> 27 ; x *= 0x94d049bb133111ebull ; x ^= x >> 31 ;
-        hi += x ;
-        uint64_t y = ((uint64_t) Ai [p] ^ 0x8EBC6AF09C88C6E3ull) * (2 * (uint64_t) p + 0x589965CC75374CC3ull) ;
-        y ^= y >> 33 ; y *= 0xff51afd7ed558ccdull ; y ^= y >> 33 ; y *= 0xc4ceb9fe1a85ec53ull ; y ^= y >> 33 ;
-        gi += y ;
+        const int64_t j1 = ((k + 1) * HASH_PIECE < ncol + 1) ? (k + 1) * HASH_PIECE : ncol + 1 ;
+        for (int64_t j = k * HASH_PIECE ; j < j1 ; j++)
+        {
+            uint64_t x = (uint64_t) Ap [j] + 0x9E3779B97F4A7C15ull * (uint64_t) (j + 1) ;
+            x ^= x >> 30 ; x *= 0xbf58476d1ce4e5b9ull ; x ^= x >> 27 ; x *= 0x94d049bb133111ebull ; x ^= x >> 31 ;
+            h += x ;
+            uint64_t y = ((uint64_t) Ap [j] ^ 0xA24BAED4963EE407ull) * (2 * (uint64_t) j + 0x632BE59BD9B4E019ull) ;
+            y ^= y >> 33 ; y *= 0xff51afd7ed558ccdull ; y ^= y >> 33 ; y *= 0xc4ceb9fe1a85ec53ull ; y ^= y >> 33 ;
+            g += y ;
+        }
+        S->hp += h ; S->gp += g ;
     }
-    S->hi += hi ; S->gi += gi ;
+    else
+    {
+        const int64_t p0 = (k - nhp) * HASH_PIECE, p1 = (p0 + HASH_PIECE < nz) ? p0 + HASH_PIECE : nz ;
+        for (int64_t p = p0 ; p < p1 ; p++)
+        {
+            uint64_t x = (uint64_t) Ai [p] + 0xD1B54A32D192ED03ull * (uint64_t) (p + 1) ;
+            x ^= x >> 30 ; x *= 0xbf58476d1ce4e5b9ull ; x ^= x >> 27 ; x *= 0x94d049bb133111ebull ; x ^= x >> 31 ;
+            h += x ;
+            uint64_t y = ((uint64_t) Ai [p] ^ 0x8EBC6AF09C88C6E3ull) * (2 * (uint64_t) p + 0x589965CC75374CC3ull) ;
+            y ^= y >> 33 ; y *= 0xff51afd7ed558ccdull ; y ^= y >> 33 ; y *= 0xc4ceb9fe1a85ec53ull ; y ^= y >> 33 ;
+            g += y ;
+        }
+        S->hi += h ; S->gi += g ;
+    }
 }
 
 static uint64_t pattern_hash_fold (cholmod_sparse *A, const pat_sums *S, uint64_t *second)
 {
     const Int ncol = (Int) A->ncol, nz = ((Int *) A->p) [ncol] ;
     uint64_t h = 0x9E3779B97F4A7C15ull ^ ((uint64_t) A->nrow * 0xff51afd7ed558ccdull) ^ ((uint64_t) (A->stype + 2) << 56) ;
-    if (second)
-    {
-        uint64_t g = S->gp ^ ((S->gi << 23) | (S->gi >> 41)) ^ ((uint64_t) nz * 0x9FB21C651E98DF25ull) ;
-        g ^= g >> 32 ; g *= 0xd6e8feb86659fd93ull ; g ^= g >> 32 ;
-        *second = g ^ ((uint64_t) ncol << 17) ;
-    }
+    uint64_t g = S->gp ^ ((S->gi << 23) | (S->gi >> 41)) ^ ((uint64_t) nz * 0x9FB21C651E98DF25ull) ;
+    g ^= g >> 32 ; g *= 0xd6e8feb86659fd93ull ; g ^= g >> 32 ;
+    *second = g ^ ((uint64_t) ncol << 17) ;
     return h ^ S->hp ^ (S->hi * 0x2545F4914F6CDD1Dull) ;
 }
 
 static uint64_t pattern_hash (cholmod_sparse *A, uint64_t *second)
 {
-    const Int *Ap = A->p, *Ai = A->i ;
-    const Int ncol = (Int) A->ncol, nz = Ap [ncol] ;
-    const int nth = api_threads () ;
-    uint64_t hp = 0, hi = 0, gp = 0, gi = 0 ;
-    const Int PIECE = (Int) 1 << 16 ;
-#pragma omp parallel for schedule(static) num_threads(nth) reduction(+:hp,gp)
-    for (Int j = 0 ; j <= ncol ; j += PIECE)
+    const int64_t npiece = hash_pieces (A) ;
+    uint64_t hp = 0, gp = 0, hi = 0, gi = 0 ;
+#pragma omp parallel for schedule(static) num_threads(api_threads ()) reduction(+:hp,gp,hi,gi)
+    for (int64_t k = 0 ; k < npiece ; k++)
     {
         pat_sums T = {0, 0, 0, 0} ;
-        pattern_hash_p (Ap, j, (j + PIECE < ncol + 1) ? j + PIECE : ncol + 1, &T) ;
-        hp += T.hp ; gp += T.gp ;
+        hash_piece (A, k, &T) ;
+        hp += T.hp ; gp += T.gp ; hi += T.hi ; gi += T.gi ;
     }
-#pragma omp parallel for schedule(static) num_threads(nth) reduction(+:hi,gi)
-    for (Int p = 0 ; p < nz ; p += PIECE)
-    {
-        pat_sums T = {0, 0, 0, 0} ;
-        pattern_hash_i (Ai, p, (p + PIECE < nz) ? p + PIECE : nz, &T) ;
-        hi += T.hi ; gi += T.gi ;
-    }
-    pat_sums S = {hp, gp, hi, gi} ;
+    const pat_sums S = {hp, gp, hi, gi} ;
     return pattern_hash_fold (A, &S, second) ;
+}
+
+/* The values-only path of cholmod_l_factorize: A has the nnz of the matrix whose S the engine holds, and only A->x travels
+ * -- staged into the plan's pinned buffer in the order the engine asks for (cholmod_hip_values_begin: by the launch that
+ * needs it, or S's own), every chunk by DMA as soon as it is full -- while the factorization is already enqueued, its
+ * clearing of L first.  The proof that the resident S and its value map fit A, the pattern hash, is taken meanwhile and
+ * checked after the fact.  Roles come from the team the runtime actually gives (a thread limit, a call from inside a
+ * parallel region: it may be smaller than asked for), so that nobody waits for work only a missing thread would do:
+ *     team >= 3: thread 0 factorizes, thread 1 pushes, the others stage; all but thread 0 then hash;
+ *     team 2:    thread 0 stages, pushes, then factorizes; thread 1 hashes;
+ *     team 1:    thread 0 does all four in that order.
+ * Returns what cholmod_l_factorize returns, or -1: take the long way -- hash [0 .. 1] then holds A's pattern hash and L
+ * no longer claims a factor on the device. */
+static int factorize_values_only (cholmod_sparse *A, double beta, cholmod_factor *L, cholmod_common *Common, uint64_t hash [2])
+{
+    cholmod_hip_plan *plan = (cholmod_hip_plan *) L->hip_plan ;
+    const int64_t annz = ((Int *) A->p) [A->ncol] ;
+    const int timing = getenv ("CHOLMOD_API_TIMING") != NULL ;
+    const double t0 = timing ? api_now () : 0 ;
+    double t1 = t0 ;
+    /* (one counter per chunk, allocated before anything is enqueued: a chunk holds at least one staging piece) */
+    const size_t maxchunk = (size_t) (annz / 16384 + 1) ;
+    int64_t *chunk_done = cholmod_l_calloc (maxchunk, sizeof (int64_t), Common) ;
+    if (!chunk_done) return FALSE ;
+    double *stage = NULL ;
+    const int64_t *index = NULL ;
+    int64_t count = 0, CH = 0 ;
+    if (cholmod_hip_values_begin (plan, &stage, &index, &count, &CH) != CHOLMOD_HIP_OK)
+    {
+        cholmod_l_free (maxchunk, sizeof (int64_t), chunk_done, Common) ;
+        forget_device_factor (L) ;          /* (the clearing of L may have been enqueued) */
+        hash [0] = pattern_hash (A, &hash [1]) ;
+        return -1 ;
+    }
+    /* staging pieces: 128 KB gathered in batch order, 256 KB copied in S order; a chunk is a whole number of pieces */
+    const int64_t PIECE = index ? 16384 : 32768 ;
+    const int fits = (count <= annz && CH >= PIECE && CH % PIECE == 0) ;     /* (the header's promise; else: cancel) */
+    const int64_t nchunk = fits ? (count + CH - 1) / CH : 0, npiece = fits ? (count + PIECE - 1) / PIECE : 0 ;
+    const int64_t nhash = hash_pieces (A) ;
+    const double *Ax = A->x ;
+    int64_t next_piece = 0, next_hash = 0, minor = (int64_t) L->n ;
+    pat_sums tot = {0, 0, 0, 0} ;
+    int rcf = CHOLMOD_HIP_OK ;
+#pragma omp parallel num_threads(api_threads ())
+    {
+        const int me = omp_get_thread_num (), team = omp_get_num_threads () ;
+        const int stager = (team >= 3) ? (me >= 2) : (me == 0), pusher = (team >= 3) ? (me == 1) : (me == 0) ;
+        const int hasher = (team >= 3) ? (me >= 1) : (me == team - 1) ;
+        if (stager)
+            for (int64_t k ; (k = __atomic_fetch_add (&next_piece, 1, __ATOMIC_RELAXED)) < npiece ; )
+            {
+                const int64_t q0 = k * PIECE, q1 = (q0 + PIECE < count) ? q0 + PIECE : count ;
+                if (!index) memcpy (stage + q0, Ax + q0, (size_t) (q1 - q0) * sizeof (double)) ;
+                else for (int64_t q = q0 ; q < q1 ; q++)
+                {
+                    /* (the index rises inside a batch: mostly the next cache lines, the prefetch covers the gaps) */
+                    if (q + 24 < q1) __builtin_prefetch (Ax + index [q + 24], 0, 0) ;
+                    stage [q] = Ax [index [q]] ;
+                }
+                __atomic_fetch_add (&chunk_done [q0 / CH], 1, __ATOMIC_RELEASE) ;
+            }
+        if (pusher)
+        {
+            if (!fits) (void) cholmod_hip_values_push_chunk (plan, -1) ;
+            for (int64_t c = 0 ; c < nchunk ; c++)
+            {
+                const int64_t o = c * CH, need = (((count - o < CH) ? count - o : CH) + PIECE - 1) / PIECE ;
+                while (__atomic_load_n (&chunk_done [c], __ATOMIC_ACQUIRE) < need) { /* (microseconds) */ }
+                if (cholmod_hip_values_push_chunk (plan, c) != CHOLMOD_HIP_OK) break ;      /* (the engine has cancelled) */
+            }
+            if (timing) t1 = api_now () ;
+        }
+        if (me == 0) rcf = cholmod_hip_factorize_resident (plan, beta, Common->quick_return_if_not_posdef, &minor) ;
+        if (hasher)
+        {
+            pat_sums mine = {0, 0, 0, 0} ;
+            for (int64_t k ; (k = __atomic_fetch_add (&next_hash, 1, __ATOMIC_RELAXED)) < nhash ; ) hash_piece (A, k, &mine) ;
+#pragma omp critical (ssamd_pattern_hash)
+            { tot.hp += mine.hp ; tot.gp += mine.gp ; tot.hi += mine.hi ; tot.gi += mine.gi ; }
+        }
+    }
+    cholmod_l_free (maxchunk, sizeof (int64_t), chunk_done, Common) ;
+    hash [0] = pattern_hash_fold (A, &tot, &hash [1]) ;
+    if (L->hip_apat_hash == hash [0] && L->hip_apat_hash2 == hash [1])
+    {
+        if (timing) fprintf (stderr, "cholmod_l_factorize (values only, in %s order): last push at %.3f ms, factorization + hash done at %.3f ms\n",
+            index ? "batch" : "S", 1e3 * (t1 - t0), 1e3 * (api_now () - t0)) ;
+        return finish_numeric (rcf, minor, L, Common) ;
+    }
+    forget_device_factor (L) ;              /* (another pattern after all: what the device computed is void) */
+    return -1 ;
 }
 
 /* reference: Cholesky/cholmod_factorize.c:97-300, supernodal symmetric branch
@@ -590,224 +685,19 @@ int cholmod_l_factorize_p (cholmod_sparse *A, double beta [2], SuiteSparse_long 
      * host-side permutation, the pattern upload and the assembly search are skipped. */
     const int vmap_ok = (A->xtype == CHOLMOD_REAL && A->packed && L->hip_plan && Common->hip_world <= 1
         && ssamd_resolve_use_gpu (Common) == 1) ;
-    uint64_t hash2 = 0, hash = 0 ;
+    uint64_t hash [2] = {0, 0} ;
     int hashed = FALSE ;
     size_t annz = vmap_ok ? (size_t) ((Int *) A->p) [A->ncol] : 0 ;
     if (vmap_ok && L->hip_apat_valid && L->hip_apat_nnz == annz && (L->xtype == CHOLMOD_REAL || L->xtype == CHOLMOD_PATTERN))
     {
-        /* The values travel first, the proof that they belong there is computed while they are on their way: A->x goes
-         * chunk by chunk into the plan's pinned staging buffer (all host threads) and every chunk leaves by DMA as soon as
-         * it is filled; the hash of the pattern is taken while the last chunks are in flight; then commit (gather on the
-         * device, the factorization's assembly waits for it -- its clearing of L runs beside the upload) or cancel. */
-        cholmod_hip_plan *plan = (cholmod_hip_plan *) L->hip_plan ;
-        double *stage = NULL ;
-        int64_t cap = 0 ;
-        const int timing = getenv ("CHOLMOD_API_TIMING") != NULL ;
-        double tq0 = timing ? api_now () : 0, tq1 = 0, tq2 = 0 ;
-        int rc = cholmod_hip_values_staging (plan, &stage, &cap) ;
-        const int nth = api_threads () ;
-        const int overlap = 1 ;
-        const int64_t *gidx = NULL ;
-        int64_t glen = 0, gcount = 0 ;
-        if (rc == CHOLMOD_HIP_OK && (size_t) cap == annz && nth >= 3 && overlap
-            && cholmod_hip_values_gather_index (plan, &gidx, &glen, &gcount) == CHOLMOD_HIP_OK && gidx && glen > 0 && gcount <= cap
-            && cholmod_hip_values_begin (plan) == CHOLMOD_HIP_OK)
-        {
-            /* Round 6, second step: the values in the order the factorization needs them.  The entries of S are staged
-             * sorted by the batch of their front (stage [k] = A->x [index [k]]: the permutation to S's order, formerly a
-             * gather kernel on the device, happens in the staging copy) and pushed chunk by chunk; the factorization --
-             * already enqueueing on thread 0, its clearing of L first -- waits before every batch for that batch's chunks
-             * only.  Thread 0: the factorization; thread 1: pushes chunks as they are complete; the others: stage, then
-             * take the pattern hash.  The hash is checked after the fact, as below. */
-            const double *Ax = A->x ;
-            const Int *Ap = A->p, *Ai = A->i ;
-            const Int ncol = (Int) A->ncol ;
-            const int64_t snz = gcount ;                    /* (one staged value per entry of S) */
-            const int64_t CH = glen, PIECE = 16384 ;        /* (glen is a multiple of PIECE: 2^20) */
-            const int64_t nchunk = (snz + CH - 1) / CH, npiece = (snz + PIECE - 1) / PIECE ;
-            const int64_t HP = (int64_t) 1 << 16 ;
-            const int64_t nhp = ((int64_t) ncol + 1 + HP - 1) / HP, nhi = ((int64_t) annz + HP - 1) / HP ;
-            int64_t *chunk_done = cholmod_l_calloc ((size_t) (nchunk > 0 ? nchunk : 1), sizeof (int64_t), Common) ;
-            int64_t next_piece = 0, next_hash = 0 ;
-            pat_sums tot = {0, 0, 0, 0} ;
-            int64_t minor = (int64_t) L->n ;
-            int rcf = CHOLMOD_HIP_OK ;
-            if (!chunk_done)
-            {
-                /* (the prologue is enqueued and a factorization is expected to follow: let it fail cleanly) */
-                (void) cholmod_hip_values_push_chunk (plan, -1) ;
-                (void) cholmod_hip_factorize_resident (plan, 0.0, 0, &minor) ;
-                return finish_numeric (CHOLMOD_HIP_OUT_OF_MEMORY, minor, L, Common) ;
-            }
-#pragma omp parallel num_threads(nth)
-            {
-                const int me = omp_get_thread_num (), team = omp_get_num_threads () ;
-                /* (a team smaller than asked for -- a thread limit, a call from inside a parallel region -- must not leave
-                 * the factorization waiting for chunks nobody pushes: thread 0 then stages and pushes everything first) */
-                const int stager = (team >= 3) ? (me >= 2) : (me == 0), pusher = (team >= 3) ? (me == 1) : (me == 0) ;
-                if (stager)
-                    for ( ; ; )
-                    {
-                        const int64_t k = __atomic_fetch_add (&next_piece, 1, __ATOMIC_RELAXED) ;
-                        if (k >= npiece) break ;
-                        const int64_t q0 = k * PIECE, q1 = (q0 + PIECE < snz) ? q0 + PIECE : snz ;
-                        for (int64_t q = q0 ; q < q1 ; q++)
-                        {
-                            /* (the index rises inside a batch: mostly the next cache lines, the prefetch covers the gaps) */
-                            if (q + 24 < q1) __builtin_prefetch (Ax + gidx [q + 24], 0, 0) ;
-                            stage [q] = Ax [gidx [q]] ;
-                        }
-                        __atomic_fetch_add (&chunk_done [q0 / CH], 1, __ATOMIC_RELEASE) ;
-                    }
-                if (pusher)
-                {
-                    for (int64_t c = 0 ; c < nchunk ; c++)
-                    {
-                        const int64_t o = c * CH, cnt = (snz - o < CH) ? snz - o : CH ;
-                        const int64_t need = (cnt + PIECE - 1) / PIECE ;
-                        while (__atomic_load_n (&chunk_done [c], __ATOMIC_ACQUIRE) < need) { /* (microseconds) */ }
-                        if (cholmod_hip_values_push_chunk (plan, c) != CHOLMOD_HIP_OK) break ;
-                    }
-                    if (timing) tq1 = api_now () ;
-                }
-                if (me == 0)
-                    rcf = cholmod_hip_factorize_resident (plan, beta ? beta [0] : 0.0, Common->quick_return_if_not_posdef, &minor) ;
-                if (me >= 1 || team == 1)
-                {
-                    pat_sums mine = {0, 0, 0, 0} ;
-                    for ( ; ; )
-                    {
-                        const int64_t k = __atomic_fetch_add (&next_hash, 1, __ATOMIC_RELAXED) ;
-                        if (k >= nhp + nhi) break ;
-                        if (k < nhp) pattern_hash_p (Ap, (Int) (k * HP), (Int) (((k + 1) * HP < ncol + 1) ? (k + 1) * HP : ncol + 1), &mine) ;
-                        else pattern_hash_i (Ai, (Int) ((k - nhp) * HP), (Int) (((k - nhp + 1) * HP < (int64_t) annz) ? (k - nhp + 1) * HP : (int64_t) annz), &mine) ;
-                    }
-#pragma omp critical (ssamd_pattern_hash)
-                    { tot.hp += mine.hp ; tot.gp += mine.gp ; tot.hi += mine.hi ; tot.gi += mine.gi ; }
-                }
-            }
-            cholmod_l_free ((size_t) (nchunk > 0 ? nchunk : 1), sizeof (int64_t), chunk_done, Common) ;
-            hash = pattern_hash_fold (A, &tot, &hash2) ;
-            hashed = TRUE ;
-            if (timing) tq2 = api_now () ;
-            if (L->hip_apat_hash == hash && L->hip_apat_hash2 == hash2)
-            {
-                if (timing) fprintf (stderr, "cholmod_l_factorize (values only, in batch order): last push at %.3f ms, factorization + hash done at %.3f ms\n",
-                    1e3 * (tq1 - tq0), 1e3 * (tq2 - tq0)) ;
-                return finish_numeric (rcf, minor, L, Common) ;
-            }
-            /* (another pattern after all: the device's S, map and factor are void; the long way rebuilds all three) */
-        }
-        else if (rc == CHOLMOD_HIP_OK && (size_t) cap == annz && nth >= 2 && overlap)
-        {
-            /* Round 6: nothing but the DMA itself stands between the call and the factorization.  Thread 0 pushes every chunk
-             * as soon as the others have staged it, commits and ENQUEUES THE FACTORIZATION AT ONCE; the other threads stage
-             * the chunks (A->x into the pinned buffer) and then take the pattern hash while the device already works.  The
-             * proof that the resident S and its value map fit A therefore arrives after the fact: should it fail -- another
-             * pattern with the same number of entries -- what the device computed is discarded and the call takes the long
-             * way (permutation, full upload, factorization), which rebuilds S, map and factor from scratch.  (Round 5: stage
-             * 1.0 ms, then the hash 1.25 ms, then the factorization: 2.7 ms on top of the nd24k stand-in's 27.9 ms step.) */
-            const double *Ax = A->x ;
-            const Int *Ap = A->p, *Ai = A->i ;
-            const Int ncol = (Int) A->ncol ;
-            const int64_t CH = (int64_t) 1 << 20 ;          /* 8 MB per push */
-            const int64_t PIECE = 32768 ;                   /* 256 KB per staging turn */
-            const int64_t nchunk = (cap + CH - 1) / CH ;
-            const int64_t npiece = (cap + PIECE - 1) / PIECE ;
-            const int64_t HP = (int64_t) 1 << 16 ;          /* entries per hash turn */
-            const int64_t nhp = ((int64_t) ncol + 1 + HP - 1) / HP, nhi = ((int64_t) annz + HP - 1) / HP ;
-            int64_t *chunk_done = cholmod_l_calloc ((size_t) (nchunk > 0 ? nchunk : 1), sizeof (int64_t), Common) ;
-            if (!chunk_done) return FALSE ;
-            int64_t next_piece = 0, next_hash = 0 ;
-            pat_sums tot = {0, 0, 0, 0} ;
-            int64_t minor = (int64_t) L->n ;
-            int rcf = CHOLMOD_HIP_OK, rcp = CHOLMOD_HIP_OK ;
-#pragma omp parallel num_threads(nth)
-            {
-                if (omp_get_thread_num () == 0)
-                {
-                    for (int64_t c = 0 ; c < nchunk && rcp == CHOLMOD_HIP_OK ; c++)
-                    {
-                        const int64_t o = c * CH, cnt = (cap - o < CH) ? cap - o : CH ;
-                        const int64_t need = (cnt + PIECE - 1) / PIECE ;
-                        while (__atomic_load_n (&chunk_done [c], __ATOMIC_ACQUIRE) < need) { /* (a few microseconds) */ }
-                        rcp = cholmod_hip_values_push (plan, o, cnt) ;
-                    }
-                    if (timing) tq1 = api_now () ;
-                    if (rcp == CHOLMOD_HIP_OK && cholmod_hip_values_commit (plan, 1) == CHOLMOD_HIP_OK)
-                        rcf = cholmod_hip_factorize_resident (plan, beta ? beta [0] : 0.0, Common->quick_return_if_not_posdef, &minor) ;
-                    else
-                    {
-                        (void) cholmod_hip_values_commit (plan, 0) ;
-                        rcp = CHOLMOD_HIP_INVALID ;
-                    }
-                }
-                else
-                {
-                    for ( ; ; )
-                    {
-                        const int64_t k = __atomic_fetch_add (&next_piece, 1, __ATOMIC_RELAXED) ;
-                        if (k >= npiece) break ;
-                        const int64_t q = k * PIECE, len = (cap - q < PIECE) ? cap - q : PIECE ;
-                        memcpy (stage + q, Ax + q, (size_t) len * sizeof (double)) ;
-                        __atomic_fetch_add (&chunk_done [q / CH], 1, __ATOMIC_RELEASE) ;
-                    }
-                    pat_sums mine = {0, 0, 0, 0} ;
-                    for ( ; ; )
-                    {
-                        const int64_t k = __atomic_fetch_add (&next_hash, 1, __ATOMIC_RELAXED) ;
-                        if (k >= nhp + nhi) break ;
-                        if (k < nhp) pattern_hash_p (Ap, (Int) (k * HP), (Int) (((k + 1) * HP < ncol + 1) ? (k + 1) * HP : ncol + 1), &mine) ;
-                        else pattern_hash_i (Ai, (Int) ((k - nhp) * HP), (Int) (((k - nhp + 1) * HP < (int64_t) annz) ? (k - nhp + 1) * HP : (int64_t) annz), &mine) ;
-                    }
-#pragma omp critical (ssamd_pattern_hash)
-                    { tot.hp += mine.hp ; tot.gp += mine.gp ; tot.hi += mine.hi ; tot.gi += mine.gi ; }
-                }
-            }
-            cholmod_l_free ((size_t) (nchunk > 0 ? nchunk : 1), sizeof (int64_t), chunk_done, Common) ;
-            hash = pattern_hash_fold (A, &tot, &hash2) ;
-            hashed = TRUE ;
-            if (timing) tq2 = api_now () ;
-            if (rcp == CHOLMOD_HIP_OK && L->hip_apat_hash == hash && L->hip_apat_hash2 == hash2)
-            {
-                if (timing) fprintf (stderr, "cholmod_l_factorize (values only, overlapped): last push at %.3f ms, factorization + hash done at %.3f ms\n",
-                    1e3 * (tq1 - tq0), 1e3 * (tq2 - tq0)) ;
-                return finish_numeric (rcf, minor, L, Common) ;
-            }
-            /* (another pattern after all: the device's S, map and factor are void; the long way rebuilds all three) */
-        }
-        else if (rc == CHOLMOD_HIP_OK && (size_t) cap == annz)
-        {
-            const double *Ax = A->x ;
-            const int64_t CH = (int64_t) 1 << 20 ;          /* 8 MB per push */
-            for (int64_t o = 0 ; o < cap && rc == CHOLMOD_HIP_OK ; o += CH)
-            {
-                const int64_t cnt = (cap - o < CH) ? cap - o : CH ;
-                const int64_t PIECE = 32768 ;               /* 256 KB per thread and turn */
-#pragma omp parallel for schedule(static) num_threads(nth) if (cnt > 4 * PIECE)
-                for (int64_t q = 0 ; q < cnt ; q += PIECE)
-                    memcpy (stage + o + q, Ax + o + q, (size_t) ((cnt - q < PIECE) ? cnt - q : PIECE) * sizeof (double)) ;
-                rc = cholmod_hip_values_push (plan, o, cnt) ;
-            }
-            if (timing) tq1 = api_now () ;
-            hash = pattern_hash (A, &hash2) ;
-            hashed = TRUE ;
-            if (timing) tq2 = api_now () ;
-            const int same = (rc == CHOLMOD_HIP_OK && L->hip_apat_hash == hash && L->hip_apat_hash2 == hash2) ;
-            if (cholmod_hip_values_commit (plan, same) == CHOLMOD_HIP_OK && same)
-            {
-                int64_t minor = (int64_t) L->n ;
-                rc = cholmod_hip_factorize_resident (plan, beta ? beta [0] : 0.0, Common->quick_return_if_not_posdef, &minor) ;
-                if (timing) fprintf (stderr, "cholmod_l_factorize (values only): stage + push %.3f ms, pattern hash %.3f ms, commit + factorization %.3f ms\n",
-                    1e3 * (tq1 - tq0), 1e3 * (tq2 - tq1), 1e3 * (api_now () - tq2)) ;
-                return finish_numeric (rc, minor, L, Common) ;
-            }
-        }
+        const int ok = factorize_values_only (A, beta ? beta [0] : 0.0, L, Common, hash) ;
+        if (ok >= 0) return ok ;
+        hashed = TRUE ;
         L->hip_apat_valid = FALSE ;         /* no usable map after all: the long way */
     }
     const int ltiming = getenv ("CHOLMOD_API_TIMING") != NULL ;
     double tl0 = ltiming ? api_now () : 0, tl1 = 0, tl2 = 0, tl3 = 0 ;
-    if (vmap_ok && !hashed) hash = pattern_hash (A, &hash2) ;
+    if (vmap_ok && !hashed) hash [0] = pattern_hash (A, &hash [1]) ;
     cholmod_sparse *S = NULL ;
     Int *src = NULL ;
     int natural = (L->ordering == CHOLMOD_NATURAL) ;
@@ -843,8 +733,8 @@ int cholmod_l_factorize_p (cholmod_sparse *A, double beta [2], SuiteSparse_long 
         if ((S == A ? id : src) && cholmod_hip_set_value_map ((cholmod_hip_plan *) L->hip_plan,
                 S == A ? id : src, (int64_t) snz, (int64_t) an) == CHOLMOD_HIP_OK)
         {
-            if (!vmap_ok) hash = pattern_hash (A, &hash2) ;
-            L->hip_apat_hash = hash ; L->hip_apat_hash2 = hash2 ;
+            if (!vmap_ok) hash [0] = pattern_hash (A, &hash [1]) ;
+            L->hip_apat_hash = hash [0] ; L->hip_apat_hash2 = hash [1] ;
             L->hip_apat_nnz = an ;
             L->hip_apat_valid = TRUE ;
         }
