@@ -261,6 +261,7 @@ typedef struct cholmod_factor_struct
                                  * complex px; CHOLMOD_HIP_CX_STORAGE) */
     void *bset_work ;           /* cholmod_l_solve2 with Bset: column -> supernode, flags (2n + 1 integers, built by the first call) */
     int hip_plan_ahead ;        /* != 0: hip_plan was built inside cholmod_l_analyze and no factorization has used it yet (plan flags + 1) */
+    int hip_perm_set ;          /* hip_plan holds L->Perm (cholmod_l_hip_solve_device hands it over on first use) */
 } cholmod_factor ;
 
 /* ---- Core ---------------------------------------------------------------- */
@@ -383,6 +384,17 @@ int cholmod_l_factor_to_host (cholmod_factor *L, cholmod_common *Common) ;
 /* Device time and per-class statistics of the last factorization
  * (CHOLMOD_HIP_NSTATS doubles, see cholmod_hip.h). */
 int cholmod_l_hip_stats (cholmod_factor *L, double *stats, cholmod_common *Common) ;
+/* cholmod_l_solve for right-hand sides that live in device memory: B_dev (n-by-nrhs doubles, column-major, leading
+ * dimension ldb, read only) and X_dev (leading dimension ldx; B_dev == X_dev with ldb == ldx is legal) are device pointers,
+ * `stream` is the caller's hipStream_t (NULL: the null stream).  The solve is ordered on that stream -- behind what the caller
+ * has enqueued, ahead of what it enqueues next -- and the host neither waits for it nor copies anything (see
+ * cholmod_hip_solve_device in cholmod_hip.h; not during stream capture).  sys: the nine codes, with the meaning
+ * cholmod_l_solve gives them for an LL' factor.  Real supernodal numeric factors with Common->useGPU on only: there is no
+ * host fallback for device pointers (Common->hip_cpu_fallback does not apply).  FALSE with CHOLMOD_INVALID for a NULL
+ * pointer, sys out of range, ld < n, a symbolic L or the GPU switched off; with CHOLMOD_NOT_INSTALLED for a complex or
+ * zomplex L -- all checked before a device is touched.  nrhs == 0 is a success that touches nothing. */
+int cholmod_l_hip_solve_device (int sys, cholmod_factor *L, const double *B_dev, size_t ldb, double *X_dev, size_t ldx,
+    size_t nrhs, void *stream, cholmod_common *Common) ;
 /* Where the relaxed fronts of an analysed L hold explicit zeros (cholmod_hip_plan_create_reach's reach_p / reach_first for
  * A's pattern and L's permutation): fills reach_p [0 .. nsuper] and, if reach_first is not NULL, reach_first; returns the
  * length of reach_first, -1 on invalid input.  cholmod_l_analyze computes the same for the plan it builds. */

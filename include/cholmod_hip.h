@@ -251,6 +251,39 @@ int cholmod_hip_upload_factor (cholmod_hip_plan *plan, const double *Lx_host) ;
 int cholmod_hip_solve (cholmod_hip_plan *plan, int which, double *X,
     int64_t nrhs, int64_t ldx) ;
 
+/* The fill-reducing permutation of the plan (n entries, a permutation of 0 .. n-1:
+ * anything else is CHOLMOD_HIP_INVALID), copied to the device once per plan so that
+ * the solve below can gather and scatter by it.  CHOLMOD_HIP_NO_DEVICE on a
+ * CHOLMOD_HIP_PLAN_HOST_ONLY plan (after the validation). */
+int cholmod_hip_set_perm (cholmod_hip_plan *plan, const int64_t *Perm) ;
+
+/* The same solves with the right-hand sides in device memory, ordered on the caller's
+ * stream: dB (n-by-nrhs, column-major, leading dimension ldb) is read only, dX
+ * (leading dimension ldx) receives the solution; dB == dX with ldb == ldx is legal
+ * (in place).  Rows n .. ld-1 of either array are neither read nor written.
+ *   which     0 = L then L', 1 = L, 2 = L', 3 = neither (permutation only)
+ *   perm_in   gather B through Perm on the way in  (y [k] = B [Perm [k]])
+ *   perm_out  scatter through Perm on the way out  (X [Perm [k]] = y [k])
+ *   stream    the caller's hipStream_t (NULL: the null stream).  The engine's stream
+ *             waits for an event recorded on it, runs the solve, and `stream` waits
+ *             for the engine's completion event: no host synchronisation, no copy
+ *             between host and device, and no allocation once the workspaces exist
+ *             (they do after the first call with fewer than 8 and the first with
+ *             more right-hand sides).  Must not be called while `stream` is being
+ *             captured into a graph.
+ * Fewer than 8 right-hand sides run the kernels of the host-array solve above on the
+ * permuted columns (a panel costs about 3.5 of their sweeps); 8 or more travel in panels
+ * of 16 (W [n][16], right-hand side fastest), L is read once per panel and the products
+ * run on v_mfma_f64_16x16x4.
+ * Needs a numeric factor on the device (several ranks: after the gather, as above) and,
+ * for perm_in / perm_out, the permutation.  CHOLMOD_HIP_INVALID for a host-only plan,
+ * NULL pointers, ld < n, nrhs < 0, a missing permutation, and for the plans of complex
+ * factors (CHOLMOD_HIP_PHI_TWIN, CHOLMOD_HIP_CX_STORAGE); nrhs == 0 is a success that
+ * touches nothing.  stats [24] is read from the solve's two events when the statistics
+ * are asked for, which may wait for the solve. */
+int cholmod_hip_solve_device (cholmod_hip_plan *plan, int which, int perm_in, int perm_out,
+    const double *dB, int64_t ldb, double *dX, int64_t ldx, int64_t nrhs, void *stream) ;
+
 /* Parity hooks: copy derived integer maps back to the host.
  *  sparent  [nsuper]     supernodal etree (reference :1025)
  *  level    [nsuper]     height of s in that tree (leaves 0)
@@ -295,7 +328,7 @@ int cholmod_hip_factor_checks_local (cholmod_hip_plan *plan, double *out5) ;
  *  [9] seconds in extend-add kernels    [10] algorithmic bytes of extend-add
  *  [11] seconds in potrf kernels        [12] seconds in trsm kernels
  *  [13] seconds in assemble (memset + A scatter)
- *  [24] device seconds of the last cholmod_hip_solve (its kernels, without the
+ *  [24] device seconds of the last solve of either kind (its kernels, without the
  *       copies of the right-hand side)
  *  [25] bytes of the all-gathers of [18] (as segments sent)   [39] those of them the main stream waits for at once: the
  *       near-row chunks of every block column and the far-row chunks of the last block column of an outer block (the other

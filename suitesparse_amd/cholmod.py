@@ -33,6 +33,7 @@ HIP_PLAN_HOST_ONLY = 2
 # plan flags (include/cholmod_hip.h)
 HIP_WIDE_OB, HIP_NO_FUSED_POTRF, HIP_NO_FUSED_TRSM, HIP_PHI_TWIN = 128, 512, 1024, 16384
 HIP_INVALID = -4
+HIP_NO_DEVICE = -1
 
 
 class Method(C.Structure):
@@ -115,7 +116,7 @@ class Factor(C.Structure):
                 ("hip_plan", C.c_void_p), ("hip_on_device", C.c_int), ("hip_host_valid", C.c_int),
                 ("cx_twin", C.c_void_p), ("hip_apat_hash", C.c_uint64), ("hip_apat_nnz", C.c_size_t),
                 ("hip_apat_valid", C.c_int), ("hip_apat_hash2", C.c_uint64), ("hip_is_twin", C.c_int),
-                ("bset_work", C.c_void_p), ("hip_plan_ahead", C.c_int)]
+                ("bset_work", C.c_void_p), ("hip_plan_ahead", C.c_int), ("hip_perm_set", C.c_int)]
 
 
 # every symbol include/cholmod.h and include/cholmod_hip.h declare
@@ -141,6 +142,7 @@ API_SYMBOLS = [
     "cholmod_l_gpu_end", "cholmod_l_gpu_allocate",
     "cholmod_l_factor_to_host", "cholmod_l_hip_stats", "cholmod_l_refactorize_resident",
     "cholmod_l_gather_factor", "cholmod_l_hip_prepare", "cholmod_l_hip_front_reach",
+    "cholmod_l_hip_solve_device",
 ]
 HIP_SYMBOLS = [
     "cholmod_hip_probe", "cholmod_hip_memorysize", "cholmod_hip_set_device", "cholmod_hip_device_count",
@@ -151,6 +153,7 @@ HIP_SYMBOLS = [
     "cholmod_hip_upload_matrix", "cholmod_hip_factorize_resident",
     "cholmod_hip_set_value_map",
     "cholmod_hip_download_factor", "cholmod_hip_download_even_columns", "cholmod_hip_upload_factor", "cholmod_hip_solve",
+    "cholmod_hip_set_perm", "cholmod_hip_solve_device",
     "cholmod_hip_get_maps", "cholmod_hip_get_stats", "cholmod_hip_set_profiling",
     
     
@@ -278,6 +281,9 @@ def lib(hooks=None):
     sig("cholmod_hip_download_factor", C.c_int, [vp, vp])
     sig("cholmod_hip_upload_factor", C.c_int, [vp, vp])
     sig("cholmod_hip_solve", C.c_int, [vp, C.c_int, vp, i64, i64])
+    sig("cholmod_hip_set_perm", C.c_int, [vp, vp])
+    sig("cholmod_hip_solve_device", C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, vp])
+    sig("cholmod_l_hip_solve_device", C.c_int, [C.c_int, fc, vp, sz, vp, sz, sz, vp, cm])
     sig("cholmod_hip_get_maps", C.c_int, [vp, vp, vp, vp])
     sig("cholmod_hip_get_stats", C.c_int, [vp, vp])
     sig("cholmod_hip_set_profiling", C.c_int, [vp, C.c_int])
@@ -460,6 +466,43 @@ class Session:
             raise RuntimeError(f"cholmod_l_solve failed, status {self.cm.status}")
         out = self.dense_to_numpy(X)
         self.free_dense(X)
+        return out
+
+    def solve_device(self, Lf, B, sys=SYS_A, out=None):
+        """cholmod_l_hip_solve_device: solve with right-hand sides that live on the device.  B: a torch.float64 device
+        tensor of shape (nrhs, n) or (n,) -- rows are right-hand sides, as in `solve` -- with unit stride along a row
+        and any row stride >= n.  Returns a device tensor of the same shape, or writes into `out` (`out is B`: in
+        place).  The solve is enqueued on torch's current stream; nothing is copied to the host and the host does not
+        wait for it.  torch must have been imported before the library was loaded (before the first Session), so that
+        the two share one HIP runtime."""
+        import torch
+        n = int(Lf.contents.n)
+        if not (isinstance(B, torch.Tensor) and B.is_cuda and B.dtype == torch.float64):
+            raise TypeError("solve_device: B must be a torch.float64 tensor on the device")
+        if B.dim() not in (1, 2) or B.shape[-1] != n:
+            raise ValueError(f"solve_device: B must have shape (nrhs, {n}) or ({n},)")
+        if out is None:
+            out = torch.empty(B.shape, dtype=torch.float64, device=B.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64
+                  and out.shape == B.shape and out.device == B.device):
+            raise ValueError("solve_device: out must be a float64 device tensor of B's shape on B's device")
+
+        def layout(t):
+            # (leading dimension, right-hand sides) of the column-major n-by-nrhs matrix the rows of t are
+            if n > 1 and t.stride(-1) != 1:
+                raise ValueError("solve_device: the entries of a right-hand side must be contiguous")
+            if t.dim() == 1 or t.shape[0] <= 1:
+                return n, (1 if t.dim() == 1 else int(t.shape[0]))
+            if t.stride(0) < n:
+                raise ValueError("solve_device: row stride smaller than n")
+            return int(t.stride(0)), int(t.shape[0])
+
+        (ldb, nrhs), (ldx, _) = layout(B), layout(out)
+        stream = torch.cuda.current_stream(B.device).cuda_stream
+        ok = self.L.cholmod_l_hip_solve_device(sys, Lf, B.data_ptr() or 1, ldb, out.data_ptr() or 1, ldx, nrhs,
+                                               stream, C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_solve_device failed, status {self.cm.status}")
         return out
 
     def solve_subset(self, Lf, b, bset, sys=SYS_A, handles=None):

@@ -360,7 +360,13 @@ struct cholmod_hip_plan {
     i64 *d_amap = nullptr ; bool amap_valid = false ;    // S entry -> index in Lx (or -1), built by the first assembly of a resident S
     // solve workspace
     double *d_X = nullptr, *d_Y = nullptr ; i64 x_cap = 0 ;
-    i64 *d_perm = nullptr ;
+    i64 *d_perm = nullptr ;                 // the fill-reducing permutation (cholmod_hip_set_perm)
+    // device-resident solve (cholmod_hip_solve_device): the panel workspace W [n][16], the accumulators of the 16-wide
+    // backward walk ([sb_max_tasks][256][16], zero between solves), the event the engine stream waits for on the
+    // caller's stream and the two that time the solve (read by cholmod_hip_get_stats)
+    double *d_sd_W = nullptr, *d_sd_acc = nullptr ; i64 sd_w_cap = 0 ;
+    hipEvent_t sd_ev_in = nullptr, sd_ev0 = nullptr, sd_ev1 = nullptr ;
+    bool sd_time_pending = false ;
     // progress of the running factorization, readable from another host thread (cholmod_hip_progress): the host side
     // counts what it has enqueued; with markers enabled the device writes, in stream order, the sequence number of the
     // exchange it has entered / left into pinned host memory (prog_dev [0] / [1])
@@ -369,7 +375,7 @@ struct cholmod_hip_plan {
     // stats
     bool profiling = false ;
     double stats [CHOLMOD_HIP_NSTATS] = {0} ;
-    double solve_seconds = 0 ;              // device time of the last cholmod_hip_solve (kernels only)
+    double solve_seconds = 0 ;              // device time of the last cholmod_hip_solve / _solve_device (kernels only)
     std::vector<float> launch_ms ;          // per-launch device time of the last profiled factorization
     hipEvent_t ev0 = nullptr, ev1 = nullptr ;
     std::vector<hipEvent_t> evpool ;

@@ -150,6 +150,7 @@ static int ensure_plan_with (cholmod_factor *L, cholmod_common *Common, const in
     if (Common->hip_allreduce)
         cholmod_hip_set_allreduce (P, Common->hip_allreduce, Common->hip_allreduce_user) ;
     L->hip_plan = P ;
+    L->hip_perm_set = FALSE ;
     return TRUE ;
 }
 
@@ -923,6 +924,42 @@ static int factor_on_device (cholmod_factor *L, cholmod_common *Common)
         L->hip_on_device = TRUE ;
     }
     return TRUE ;
+}
+
+/* cholmod_l_solve with B and X in device memory, ordered on the caller's stream (cholmod.h) */
+int cholmod_l_hip_solve_device (int sys, cholmod_factor *L, const double *B_dev, size_t ldb, double *X_dev, size_t ldx,
+    size_t nrhs, void *stream, cholmod_common *Common)
+{
+    RETURN_IF_NULL_COMMON (FALSE) ;
+    RETURN_IF_NULL (L, FALSE) ;
+    RETURN_IF_NULL (B_dev, FALSE) ;
+    RETURN_IF_NULL (X_dev, FALSE) ;
+    if (sys < CHOLMOD_A || sys > CHOLMOD_Pt) { ERROR (CHOLMOD_INVALID, "invalid system") ; return FALSE ; }
+    if (ldb < L->n || ldx < L->n) { ERROR (CHOLMOD_INVALID, "leading dimension smaller than n") ; return FALSE ; }
+    if (L->xtype == CHOLMOD_COMPLEX || L->xtype == CHOLMOD_ZOMPLEX)
+    { ERROR (CHOLMOD_NOT_INSTALLED, "a device solve with a complex factor is not supported") ; return FALSE ; }
+    if (L->xtype != CHOLMOD_REAL || !L->is_super)
+    { ERROR (CHOLMOD_INVALID, "L must be a numeric supernodal factor") ; return FALSE ; }
+    /* device pointers cannot be solved against on the host: no fallback, whatever Common->hip_cpu_fallback says */
+    if (ssamd_resolve_use_gpu (Common) != 1) { ERROR (CHOLMOD_INVALID, "a device solve needs Common->useGPU") ; return FALSE ; }
+    Common->status = CHOLMOD_OK ;
+    if (!factor_on_device (L, Common)) return FALSE ;
+    if (nrhs == 0 || L->n == 0) return TRUE ;
+    cholmod_hip_plan *plan = (cholmod_hip_plan *) L->hip_plan ;
+    /* what the engine does for each system (as cholmod_l_solve2 below does on the host) */
+    const int perm_in = (sys == CHOLMOD_A || sys == CHOLMOD_P), perm_out = (sys == CHOLMOD_A || sys == CHOLMOD_Pt) ;
+    const int which = (sys == CHOLMOD_A || sys == CHOLMOD_LDLt) ? 0
+                    : (sys == CHOLMOD_L || sys == CHOLMOD_LD) ? 1
+                    : (sys == CHOLMOD_Lt || sys == CHOLMOD_DLt) ? 2 : 3 ;
+    if ((perm_in || perm_out) && !L->hip_perm_set)
+    {
+        int rc = cholmod_hip_set_perm (plan, (const int64_t *) L->Perm) ;
+        if (rc != CHOLMOD_HIP_OK) return map_hip_status (rc, Common, "the permutation could not be stored on the device") ;
+        L->hip_perm_set = TRUE ;
+    }
+    int rc = cholmod_hip_solve_device (plan, which, perm_in, perm_out, B_dev, (int64_t) ldb, X_dev, (int64_t) ldx,
+        (int64_t) nrhs, stream) ;
+    return (rc == CHOLMOD_HIP_OK) ? TRUE : map_hip_status (rc, Common, "HIP device solve failed") ;
 }
 
 /* the triangular solves run where the factor is: on the host when the values are
