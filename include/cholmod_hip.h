@@ -243,7 +243,8 @@ int cholmod_hip_download_even_columns (cholmod_hip_plan *plan, double *out_host)
  * elsewhere), so the device solves can be used with it. */
 int cholmod_hip_upload_factor (cholmod_hip_plan *plan, const double *Lx_host) ;
 
-/* Supernodal triangular solves on the device-resident factor, in place on the
+/* (This entry point and the two after it: csrc/hip/solve.hip.)
+ * Supernodal triangular solves on the device-resident factor, in place on the
  * host array X (n-by-nrhs, leading dimension ldx), in the permuted ordering:
  * replace cholmod_l_super_lsolve / cholmod_l_super_ltsolve
  * (CHOLMOD/Supernodal/t_cholmod_super_solve.c:14-220, :222-411).

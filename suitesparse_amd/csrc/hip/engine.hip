@@ -1,8 +1,7 @@
 // engine.hip -- host side of the MI355X supernodal Cholesky engine that touches the device: upload of a plan
 // (plan_build.hip / schedule_dense.hip derive it), the runner of its launch list, the exchange over RCCL, the gather,
-// the triangular solves, and the extern "C" shim declared in include/cholmod_hip.h.  One process drives one GPU.
+// and the extern "C" shim declared in include/cholmod_hip.h (the triangular solves: solve.hip).  One process drives one GPU.
 #include "kernels.hip.h"
-#include "solve_block_kernels.hip.h"
 #include "plan.hip.h"
 #include <thread>
 
@@ -44,8 +43,6 @@ RcclApi *rccl_api ()
 }
 } // namespace sship
 #define COMMA ,
-// (solves, checks) K<true> for a complex factor in its own storage; needs `cxs` in scope
-#define CXS_LAUNCH(K, ...) do { if (cxs) hipLaunchKernelGGL (K<true>, __VA_ARGS__) ; else hipLaunchKernelGGL (K<false>, __VA_ARGS__) ; } while (0)
 #define RCCLCHK(call) do { ncclResult_t r_ = (call) ; if (r_ != ncclSuccess) { \
     fprintf (stderr, "cholmod_hip: %s failed: %s (%s:%d)\n", #call, \
         (rccl_api () && rccl_api ()->GetErrorString) ? rccl_api ()->GetErrorString (r_) : "?", __FILE__, __LINE__) ; \
@@ -70,8 +67,8 @@ static void free_device (cholmod_hip_plan *P)
     if (P->ar_done) (void) hipEventDestroy (P->ar_done) ;
     void *ptrs [] = {P->d_Ls, P->d_fr, P->d_supermap, P->d_child, P->d_relmap, P->d_info,
         P->d_lvl_list, P->d_Lx, P->d_cb, P->d_zg, P->d_eg, P->d_pg, P->d_tg, P->d_tu_cnt, P->d_cdesc, P->d_smd, P->d_sp01, P->d_gg, P->d_sm,
-        P->d_Sp, P->d_Si, P->d_Snz, P->d_Sx, P->d_amap, P->d_X, P->d_Y, P->d_perm, P->d_xchg, P->d_stage, P->d_ag, P->d_agf, P->d_Lx_full, P->d_fr_full, P->d_dg, P->d_rg, P->d_wg, P->d_cg, P->d_cflags, P->d_crel, P->d_relpairs, P->d_dinv, P->d_sv,
-        P->d_inv_tasks, P->d_winv, P->d_solved, P->d_sv_acc, P->d_sd_W, P->d_sd_acc, P->d_ticket, P->d_chk, P->d_chk_out, P->d_thin_tim, P->d_sb_tasks, P->d_sb_commit, P->d_first_fail, P->d_vsrc, P->d_vals,
+        P->d_Sp, P->d_Si, P->d_Snz, P->d_Sx, P->d_amap, P->d_X, P->d_perm, P->d_xchg, P->d_stage, P->d_ag, P->d_agf, P->d_Lx_full, P->d_fr_full, P->d_dg, P->d_rg, P->d_wg, P->d_cg, P->d_cflags, P->d_crel, P->d_relpairs, P->d_dinv, P->d_sv,
+        P->d_inv_tasks, P->d_winv, P->d_solved, P->d_sv_acc, P->d_sd_W, P->d_sd_acc, P->d_chk, P->d_chk_out, P->d_thin_tim, P->d_sb_tasks, P->d_sb_commit, P->d_first_fail, P->d_vsrc, P->d_vals,
         P->d_xg, P->d_gmap} ;
     for (void *p : ptrs) if (p) (void) hipFree (p) ;
     for (auto e : P->evpool) (void) hipEventDestroy (e) ;
@@ -879,11 +876,6 @@ static int run_factorize (cholmod_hip_plan *P, double beta, int quick, i64 *mino
 
 } // namespace
 
-// The complete numeric factor in the reference layout and the descriptors that go with it: the
-// rank's own array when there is one rank, the gathered copy otherwise (nullptr before a gather).
-static double *whole_factor (cholmod_hip_plan *P) { return P->world == 1 ? P->d_Lx : (P->full_valid ? P->d_Lx_full : nullptr) ; }
-static const FrontD *whole_fronts (cholmod_hip_plan *P) { return P->world == 1 ? P->d_fr : P->d_fr_full ; }
-
 // ============================================================================
 // extern "C" shim
 // ============================================================================
@@ -1671,345 +1663,6 @@ int cholmod_hip_factorize (cholmod_hip_plan *P, const int64_t *Sp, const int64_t
         if (rc2 != CHOLMOD_HIP_OK) return rc2 ;
     }
     return rc ;
-}
-
-int cholmod_hip_solve (cholmod_hip_plan *P, int which, double *X, int64_t nrhs, int64_t ldx)
-{
-    if (!P || P->host_only || !X || nrhs < 0 || ldx < P->n) return CHOLMOD_HIP_INVALID ;
-    if (nrhs == 0 || P->n == 0) return CHOLMOD_HIP_OK ;
-    const double *Lw = whole_factor (P) ;
-    const FrontD *frw = whole_fronts (P) ;
-    if (!Lw || !frw) return CHOLMOD_HIP_INVALID ;  // several ranks: cholmod_hip_gather_factor first
-    const bool cxs = (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;
-    i64 need = ldx * nrhs ;
-    if (need > P->x_cap)
-    {
-        if (P->d_X) (void) hipFree (P->d_X) ;
-        P->d_X = nullptr ;
-        HIPCHK (hipMalloc ((void **) &P->d_X, need * sizeof (double))) ;
-        P->x_cap = need ;
-    }
-    hipStream_t st = P->stream ;
-    // workspace of the big-supernode walk
-    if (!P->inv_tasks.empty ())
-    {
-        if (!P->d_winv)
-        {
-            hipError_t e ;
-            HIPCHK (hipMalloc ((void **) &P->d_winv, P->inv_tasks.size () * 8192 * sizeof (double))) ;
-            P->d_inv_tasks = dupload (P->inv_tasks, e) ; HIPCHK (e) ;
-            P->d_sb_tasks = dupload (P->sb_tasks, e) ; HIPCHK (e) ;
-            P->d_sb_commit = dupload (P->sb_commit, e) ; HIPCHK (e) ;
-            HIPCHK (hipMalloc ((void **) &P->d_ticket, (size_t) std::max (P->sb_max_tasks, 1) * sizeof (unsigned int))) ;
-            HIPCHK (hipMemset (P->d_ticket, 0, (size_t) std::max (P->sb_max_tasks, 1) * sizeof (unsigned int))) ;
-            P->winv_valid = false ;
-        }
-        if (need > P->solved_cap)
-        {
-            if (P->d_solved) (void) hipFree (P->d_solved) ;
-            P->d_solved = nullptr ;
-            P->solved_cap = need ;
-            HIPCHK (hipMalloc ((void **) &P->d_solved, P->solved_cap * sizeof (double))) ;
-        }
-        if ((i64) P->sb_max_tasks * SOLVE_SB * nrhs > P->sv_acc_cap)
-        {
-            if (P->d_sv_acc) (void) hipFree (P->d_sv_acc) ;
-            P->d_sv_acc = nullptr ;
-            P->sv_acc_cap = (i64) P->sb_max_tasks * SOLVE_SB * nrhs ;
-            HIPCHK (hipMalloc ((void **) &P->d_sv_acc, P->sv_acc_cap * sizeof (double))) ;
-            HIPCHK (hipMemset (P->d_sv_acc, 0, P->sv_acc_cap * sizeof (double))) ;
-        }
-        if (!P->winv_valid)
-        {
-            CXS_LAUNCH (k_diag_inv64, dim3 ((unsigned) P->inv_tasks.size ()), dim3 (64), 0, st,
-                P->d_inv_tasks, frw, Lw, P->d_winv) ;
-            P->winv_valid = true ;
-        }
-    }
-    HIPCHK (hipMemcpyAsync (P->d_X, X, need * sizeof (double), hipMemcpyHostToDevice, st)) ;
-    HIPCHK (hipEventRecord (P->ev0, st)) ;
-    if (which == 0 || which == 1)
-    {
-        for (int l = 0 ; l < P->nlevels ; l++)
-        {
-            int nf = P->sv_ptr [l+1] - P->sv_ptr [l] ;
-            if (nf) CXS_LAUNCH (k_lsolve, dim3 (nf), dim3 (256), 0, st,
-                P->d_sv + P->sv_ptr [l], frw, P->d_Ls, Lw, P->d_X, (i64) ldx, (int) nrhs) ;
-            for (int q = P->sb_lvl_ptr [l] ; q < P->sb_lvl_ptr [l+1] ; q++)
-            {
-                const auto &B = P->sb_launch [q] ;
-                CXS_LAUNCH (k_solve_fwd_diag, dim3 (B.ntasks), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, frw, Lw, P->d_winv, P->d_X, (i64) ldx, (int) nrhs, P->d_solved) ;
-                if (B.grid > 0) CXS_LAUNCH (k_solve_fwd_apply, dim3 (B.grid), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, (int) B.ntasks, frw, P->d_Ls, Lw,
-                    P->d_X, (i64) ldx, (int) nrhs, P->d_solved) ;
-            }
-            const auto &Cm = P->sb_commit_launch [l] ;
-            if (Cm.ntasks) hipLaunchKernelGGL (k_solve_commit, dim3 (Cm.grid), dim3 (256), 0, st,
-                P->d_sb_commit + Cm.first, (int) Cm.ntasks, frw, P->d_X, (i64) ldx, (int) nrhs, P->d_solved) ;
-        }
-    }
-    if (which == 0 || which == 2)
-    {
-        for (int l = P->nlevels - 1 ; l >= 0 ; l--)
-        {
-            for (int q = P->sb_lvl_ptr [l+1] - 1 ; q >= P->sb_lvl_ptr [l] ; q--)
-            {
-                const auto &B = P->sb_launch [q] ;
-                if (B.grid > 0) CXS_LAUNCH (k_solve_bwd_apply, dim3 (B.grid), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, (int) B.ntasks, frw, P->d_Ls, Lw,
-                    P->d_X, (i64) ldx, (int) nrhs, P->d_sv_acc) ;
-                CXS_LAUNCH (k_solve_bwd_diag, dim3 (B.ntasks), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, frw, Lw, P->d_winv, P->d_X, (i64) ldx, (int) nrhs, P->d_sv_acc) ;
-            }
-            int nf = P->sv_ptr [l+1] - P->sv_ptr [l] ;
-            if (nf) CXS_LAUNCH (k_ltsolve, dim3 (nf), dim3 (256), 0, st,
-                P->d_sv + P->sv_ptr [l], frw, P->d_Ls, Lw, P->d_X, (i64) ldx, (int) nrhs) ;
-        }
-    }
-    HIPCHK (hipGetLastError ()) ;
-    HIPCHK (hipEventRecord (P->ev1, st)) ;
-    HIPCHK (hipMemcpyAsync (X, P->d_X, need * sizeof (double), hipMemcpyDeviceToHost, st)) ;
-    HIPCHK (hipStreamSynchronize (st)) ;
-    {
-        float ms = 0 ;
-        if (hipEventElapsedTime (&ms, P->ev0, P->ev1) == hipSuccess) P->solve_seconds = 1e-3 * ms ;
-    }
-    return CHOLMOD_HIP_OK ;
-}
-
-// ---- solves whose right-hand sides live in HBM ---------------------------------------------------------------------------
-
-int cholmod_hip_set_perm (cholmod_hip_plan *P, const int64_t *Perm)
-{
-    if (!P || !Perm) return CHOLMOD_HIP_INVALID ;
-    const i64 n = P->n ;
-    {
-        // a permutation of 0 .. n-1, checked before anything on the device may index with it
-        std::vector<char> seen ((size_t) std::max<i64> (n, 1), 0) ;
-        for (i64 k = 0 ; k < n ; k++)
-        {
-            const i64 p = Perm [k] ;
-            if (p < 0 || p >= n || seen [p]) return CHOLMOD_HIP_INVALID ;
-            seen [p] = 1 ;
-        }
-    }
-    if (P->host_only) return CHOLMOD_HIP_NO_DEVICE ;
-    if (!P->d_perm) HIPCHK (hipMalloc ((void **) &P->d_perm, std::max<i64> (n, 1) * sizeof (i64))) ;
-    // (a solve in flight on the engine stream may still read the old one)
-    HIPCHK (hipStreamSynchronize (P->stream)) ;
-    if (n) HIPCHK (hipMemcpy (P->d_perm, Perm, n * sizeof (i64), hipMemcpyHostToDevice)) ;
-    return CHOLMOD_HIP_OK ;
-}
-
-// first nrhs that takes the 16-wide kernels.  A panel costs what about 3.5 sweeps of the one-column kernels cost
-// (Poisson 100^3: 31 ms against 9.2 ms; its walk over the big supernodes is as latency-bound as theirs), and they
-// take about 4.6 ms per further column: the panel wins from 6 - 8 right-hand sides on the 3D problems, from 4 on
-// the 2D one (profiles/solve_device_times.json).  Below it the right-hand sides run column by column.
-#define SD_BLOCK_MIN_NRHS 8
-
-// workspaces of a device-resident solve; nothing is allocated once they exist
-static int sd_ensure (cholmod_hip_plan *P, bool with_factor, bool columns)
-{
-    const i64 n = P->n ;
-    if (!P->sd_ev_in)
-    {
-        HIPCHK (hipEventCreateWithFlags (&P->sd_ev_in, hipEventDisableTiming)) ;
-        HIPCHK (hipEventCreate (&P->sd_ev0)) ;
-        HIPCHK (hipEventCreate (&P->sd_ev1)) ;
-    }
-    if (!P->d_sd_W)
-    {
-        HIPCHK (hipMalloc ((void **) &P->d_sd_W, (size_t) n * SD_NP * sizeof (double))) ;
-        P->sd_w_cap = n * SD_NP ;
-    }
-    if (!with_factor || P->inv_tasks.empty ()) return CHOLMOD_HIP_OK ;
-    if (!P->d_winv)
-    {
-        // (as cholmod_hip_solve: the two share the inverses and the task lists)
-        hipError_t e ;
-        HIPCHK (hipMalloc ((void **) &P->d_winv, P->inv_tasks.size () * 8192 * sizeof (double))) ;
-        P->d_inv_tasks = dupload (P->inv_tasks, e) ; HIPCHK (e) ;
-        P->d_sb_tasks = dupload (P->sb_tasks, e) ; HIPCHK (e) ;
-        P->d_sb_commit = dupload (P->sb_commit, e) ; HIPCHK (e) ;
-        HIPCHK (hipMalloc ((void **) &P->d_ticket, (size_t) std::max (P->sb_max_tasks, 1) * sizeof (unsigned int))) ;
-        HIPCHK (hipMemset (P->d_ticket, 0, (size_t) std::max (P->sb_max_tasks, 1) * sizeof (unsigned int))) ;
-        P->winv_valid = false ;
-    }
-    if (columns)
-    {
-        // a few right-hand sides run the kernels of cholmod_hip_solve: its side vector and accumulators, sized once
-        // for the most that come this way
-        const i64 most = SD_BLOCK_MIN_NRHS - 1 ;
-        if (n * most > P->solved_cap)
-        {
-            if (P->d_solved) (void) hipFree (P->d_solved) ;
-            P->d_solved = nullptr ;
-            P->solved_cap = n * most ;
-            HIPCHK (hipMalloc ((void **) &P->d_solved, P->solved_cap * sizeof (double))) ;
-        }
-        if ((i64) P->sb_max_tasks * SOLVE_SB * most > P->sv_acc_cap)
-        {
-            if (P->d_sv_acc) (void) hipFree (P->d_sv_acc) ;
-            P->d_sv_acc = nullptr ;
-            P->sv_acc_cap = (i64) P->sb_max_tasks * SOLVE_SB * most ;
-            HIPCHK (hipMalloc ((void **) &P->d_sv_acc, P->sv_acc_cap * sizeof (double))) ;
-            HIPCHK (hipMemset (P->d_sv_acc, 0, P->sv_acc_cap * sizeof (double))) ;
-        }
-    }
-    else if (!P->d_sd_acc)
-    {
-        const size_t bytes = (size_t) std::max (P->sb_max_tasks, 1) * SOLVE_SB * SD_NP * sizeof (double) ;
-        HIPCHK (hipMalloc ((void **) &P->d_sd_acc, bytes)) ;
-        HIPCHK (hipMemset (P->d_sd_acc, 0, bytes)) ;
-    }
-    return CHOLMOD_HIP_OK ;
-}
-
-// a few right-hand sides, in place on the permuted columns x [nrhs][n]: the launches of cholmod_hip_solve
-static void sd_sweeps_columns (cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, double *x, int nrhs, hipStream_t st)
-{
-    const bool cxs = false ;
-    const i64 ldx = P->n ;
-    if (which == 0 || which == 1)
-    {
-        for (int l = 0 ; l < P->nlevels ; l++)
-        {
-            int nf = P->sv_ptr [l+1] - P->sv_ptr [l] ;
-            if (nf) CXS_LAUNCH (k_lsolve, dim3 (nf), dim3 (256), 0, st,
-                P->d_sv + P->sv_ptr [l], frw, P->d_Ls, Lw, x, ldx, nrhs) ;
-            for (int q = P->sb_lvl_ptr [l] ; q < P->sb_lvl_ptr [l+1] ; q++)
-            {
-                const auto &B = P->sb_launch [q] ;
-                CXS_LAUNCH (k_solve_fwd_diag, dim3 (B.ntasks), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, frw, Lw, P->d_winv, x, ldx, nrhs, P->d_solved) ;
-                if (B.grid > 0) CXS_LAUNCH (k_solve_fwd_apply, dim3 (B.grid), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, (int) B.ntasks, frw, P->d_Ls, Lw, x, ldx, nrhs, P->d_solved) ;
-            }
-            const auto &Cm = P->sb_commit_launch [l] ;
-            if (Cm.ntasks) hipLaunchKernelGGL (k_solve_commit, dim3 (Cm.grid), dim3 (256), 0, st,
-                P->d_sb_commit + Cm.first, (int) Cm.ntasks, frw, x, ldx, nrhs, P->d_solved) ;
-        }
-    }
-    if (which == 0 || which == 2)
-    {
-        for (int l = P->nlevels - 1 ; l >= 0 ; l--)
-        {
-            for (int q = P->sb_lvl_ptr [l+1] - 1 ; q >= P->sb_lvl_ptr [l] ; q--)
-            {
-                const auto &B = P->sb_launch [q] ;
-                if (B.grid > 0) CXS_LAUNCH (k_solve_bwd_apply, dim3 (B.grid), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, (int) B.ntasks, frw, P->d_Ls, Lw, x, ldx, nrhs, P->d_sv_acc) ;
-                CXS_LAUNCH (k_solve_bwd_diag, dim3 (B.ntasks), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, frw, Lw, P->d_winv, x, ldx, nrhs, P->d_sv_acc) ;
-            }
-            int nf = P->sv_ptr [l+1] - P->sv_ptr [l] ;
-            if (nf) CXS_LAUNCH (k_ltsolve, dim3 (nf), dim3 (256), 0, st,
-                P->d_sv + P->sv_ptr [l], frw, P->d_Ls, Lw, x, ldx, nrhs) ;
-        }
-    }
-}
-
-// a panel of up to 16 right-hand sides, in place on W [n][16]: the same schedule, L read once
-static void sd_sweeps_panel (cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, double *W, hipStream_t st)
-{
-    if (which == 0 || which == 1)
-    {
-        for (int l = 0 ; l < P->nlevels ; l++)
-        {
-            int nf = P->sv_ptr [l+1] - P->sv_ptr [l] ;
-            if (nf) hipLaunchKernelGGL (k_sd_lsolve, dim3 (nf), dim3 (256), 0, st,
-                P->d_sv + P->sv_ptr [l], frw, P->d_Ls, Lw, W) ;
-            for (int q = P->sb_lvl_ptr [l] ; q < P->sb_lvl_ptr [l+1] ; q++)
-            {
-                const auto &B = P->sb_launch [q] ;
-                hipLaunchKernelGGL (k_sd_fwd_diag, dim3 (B.ntasks), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, frw, Lw, P->d_winv, W) ;
-                if (B.grid > 0) hipLaunchKernelGGL (k_sd_fwd_apply, dim3 (B.grid), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, (int) B.ntasks, frw, P->d_Ls, Lw, W) ;
-            }
-        }
-    }
-    if (which == 0 || which == 2)
-    {
-        for (int l = P->nlevels - 1 ; l >= 0 ; l--)
-        {
-            for (int q = P->sb_lvl_ptr [l+1] - 1 ; q >= P->sb_lvl_ptr [l] ; q--)
-            {
-                const auto &B = P->sb_launch [q] ;
-                if (B.grid > 0) hipLaunchKernelGGL (k_sd_bwd_apply, dim3 (B.grid), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, (int) B.ntasks, frw, P->d_Ls, Lw, W, P->d_sd_acc) ;
-                hipLaunchKernelGGL (k_sd_bwd_diag, dim3 (B.ntasks), dim3 (256), 0, st,
-                    P->d_sb_tasks + B.first, frw, Lw, P->d_winv, W, P->d_sd_acc) ;
-            }
-            int nf = P->sv_ptr [l+1] - P->sv_ptr [l] ;
-            if (nf) hipLaunchKernelGGL (k_sd_ltsolve, dim3 (nf), dim3 (256), 0, st,
-                P->d_sv + P->sv_ptr [l], frw, P->d_Ls, Lw, W) ;
-        }
-    }
-}
-
-int cholmod_hip_solve_device (cholmod_hip_plan *P, int which, int perm_in, int perm_out, const double *dB, int64_t ldb,
-    double *dX, int64_t ldx, int64_t nrhs, void *stream)
-{
-    if (!P || P->host_only || !dB || !dX || nrhs < 0 || ldb < P->n || ldx < P->n || which < 0 || which > 3)
-        return CHOLMOD_HIP_INVALID ;
-    if (P->flags & (CHOLMOD_HIP_CX_STORAGE | CHOLMOD_HIP_PHI_TWIN)) return CHOLMOD_HIP_INVALID ;     // real factors only
-    if ((perm_in || perm_out) && !P->d_perm) return CHOLMOD_HIP_INVALID ;       // cholmod_hip_set_perm first
-    const i64 n = P->n ;
-    if (nrhs == 0 || n == 0) return CHOLMOD_HIP_OK ;
-    const double *Lw = nullptr ;
-    const FrontD *frw = nullptr ;
-    if (which != 3)
-    {
-        Lw = whole_factor (P) ;
-        frw = whole_fronts (P) ;
-        if (!Lw || !frw) return CHOLMOD_HIP_INVALID ;  // several ranks: cholmod_hip_gather_factor first
-    }
-    const bool columns = nrhs < SD_BLOCK_MIN_NRHS ;
-    { int rc = sd_ensure (P, which != 3, columns) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
-    hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    // the engine stream takes its place in the caller's order: behind what the caller has enqueued ...
-    HIPCHK (hipEventRecord (P->sd_ev_in, user)) ;
-    HIPCHK (hipStreamWaitEvent (st, P->sd_ev_in, 0)) ;
-    if (which != 3 && !P->inv_tasks.empty () && !P->winv_valid)
-    {
-        hipLaunchKernelGGL (k_diag_inv64<false>, dim3 ((unsigned) P->inv_tasks.size ()), dim3 (64), 0, st,
-            P->d_inv_tasks, frw, Lw, P->d_winv) ;
-        P->winv_valid = true ;
-    }
-    HIPCHK (hipEventRecord (P->sd_ev0, st)) ;
-    const i64 *pin = perm_in ? P->d_perm : nullptr, *pout = perm_out ? P->d_perm : nullptr ;
-    const unsigned nblk = (unsigned) ((n + 255) / 256) ;
-    double *W = P->d_sd_W ;
-    if (columns)
-    {
-        // directly on the permuted columns, W as [nrhs][n]
-        if (pin) for (i64 r = 0 ; r < nrhs ; r++)
-            hipLaunchKernelGGL (k_perm, dim3 (nblk), dim3 (256), 0, st, n, pin, dB + r * ldb, W + r * n, 0) ;
-        else HIPCHK (hipMemcpy2DAsync (W, n * sizeof (double), dB, ldb * sizeof (double), n * sizeof (double), (size_t) nrhs,
-            hipMemcpyDeviceToDevice, st)) ;
-        if (which != 3) sd_sweeps_columns (P, which, frw, Lw, W, (int) nrhs, st) ;
-        if (pout) for (i64 r = 0 ; r < nrhs ; r++)
-            hipLaunchKernelGGL (k_perm, dim3 (nblk), dim3 (256), 0, st, n, pout, (const double *) (W + r * n), dX + r * ldx, 1) ;
-        else HIPCHK (hipMemcpy2DAsync (dX, ldx * sizeof (double), W, n * sizeof (double), n * sizeof (double), (size_t) nrhs,
-            hipMemcpyDeviceToDevice, st)) ;
-    }
-    else for (i64 r0 = 0 ; r0 < nrhs ; r0 += SD_NP)
-    {
-        const int pw = (int) std::min<i64> (SD_NP, nrhs - r0) ;
-        hipLaunchKernelGGL (k_sd_pack, dim3 (nblk), dim3 (256), 0, st, n, pin, dB + r0 * ldb, (i64) ldb, pw, W) ;
-        if (which != 3) sd_sweeps_panel (P, which, frw, Lw, W, st) ;
-        hipLaunchKernelGGL (k_sd_unpack, dim3 (nblk), dim3 (256), 0, st, n, pout, (const double *) W, pw, dX + r0 * ldx, (i64) ldx) ;
-    }
-    HIPCHK (hipGetLastError ()) ;
-    HIPCHK (hipEventRecord (P->sd_ev1, st)) ;
-    // ... and ahead of what the caller enqueues next
-    HIPCHK (hipStreamWaitEvent (user, P->sd_ev1, 0)) ;
-    // stats [24]: the two events are read by cholmod_hip_get_stats (a cholmod_hip_solve in between overwrites the mark)
-    P->solve_seconds = -1.0 ;
-    P->sd_time_pending = true ;
-    return CHOLMOD_HIP_OK ;
 }
 
 static int ensure_check_tasks (cholmod_hip_plan *P) ;

@@ -1,7 +1,7 @@
 // plan.hip.h -- the types the host-side translation units of the engine share: the launch list (Launch, Schedule), the
 // contribution-block arena allocator, the RCCL entry points bound at run time, and the plan itself (cholmod_hip_plan:
 // one symbolic factor prepared for one rank).  plan_build.hip derives the plan (etree, ownership, layout, batches),
-// schedule_dense.hip the launches of a batch of fronts, engine.hip uploads and runs it.
+// schedule_dense.hip the launches of a batch of fronts, engine.hip uploads and runs it, solve.hip solves with its factor.
 #pragma once
 #include "descriptors.hip.h"
 #include "../../../include/cholmod_hip.h"
@@ -102,6 +102,8 @@ struct Launch {
 #define HIPCHK(call) do { hipError_t e_ = (call) ; if (e_ != hipSuccess) { \
     fprintf (stderr, "cholmod_hip: %s failed: %s (%s:%d)\n", #call, \
         hipGetErrorString (e_), __FILE__, __LINE__) ; return CHOLMOD_HIP_GPU_PROBLEM ; } } while (0)
+// (solves, checks) K<true> for a complex factor in its own storage; needs `cxs` in scope
+#define CXS_LAUNCH(K, ...) do { if (cxs) hipLaunchKernelGGL (K<true>, __VA_ARGS__) ; else hipLaunchKernelGGL (K<false>, __VA_ARGS__) ; } while (0)
 
 // best-fit free-list allocator for the contribution-block arena (plan time)
 struct Arena {
@@ -258,8 +260,9 @@ struct cholmod_hip_plan {
     double *d_ag = nullptr ;                // the g solved near-row chunks of a block column (all-gather, in place)
     double *d_agf = nullptr ;               // ... its far-row chunks (a gather of its own, on the exchange stream)
     i64 stage_len = 0, ag_len = 0, agf_len = 0 ;
-    // triangular solves: per level, the supernodes one workgroup handles whole
-    // and the big ones walked in SOLVE_SB-column blocks by many workgroups (k_solve_*_blk)
+    // triangular solves: per level, the supernodes one workgroup handles whole (k_lsolve / k_ltsolve, k_sd_lsolve /
+    // k_sd_ltsolve) and the big ones walked in SOLVE_SB-column blocks by many workgroups (k_solve_fwd_* / k_solve_bwd_*,
+    // k_sd_fwd_* / k_sd_bwd_*)
     std::vector<SolveTask> sv_tasks ;       // [whole-supernode tasks by level | block tasks]
     std::vector<i32> sv_ptr ;               // level -> range of whole-supernode tasks
     std::vector<std::vector<i32>> sv_big ;  // level -> big supernodes
@@ -273,7 +276,6 @@ struct cholmod_hip_plan {
     bool winv_valid = false ;
     double *d_solved = nullptr ; i64 solved_cap = 0 ;     // side vector Y of the forward walk
     double *d_sv_acc = nullptr ; i64 sv_acc_cap = 0 ;
-    unsigned int *d_ticket = nullptr ;
     // the walk, batched over the big supernodes of a level: step b of a level = one
     // launch holding block b of every big supernode of the level that has one
     struct SbLaunch { i32 level, first, ntasks, grid ; } ;
@@ -359,12 +361,12 @@ struct cholmod_hip_plan {
     int cur_mapped = 0 ;
     i64 *d_amap = nullptr ; bool amap_valid = false ;    // S entry -> index in Lx (or -1), built by the first assembly of a resident S
     // solve workspace
-    double *d_X = nullptr, *d_Y = nullptr ; i64 x_cap = 0 ;
+    double *d_X = nullptr ; i64 x_cap = 0 ;
     i64 *d_perm = nullptr ;                 // the fill-reducing permutation (cholmod_hip_set_perm)
     // device-resident solve (cholmod_hip_solve_device): the panel workspace W [n][16], the accumulators of the 16-wide
     // backward walk ([sb_max_tasks][256][16], zero between solves), the event the engine stream waits for on the
     // caller's stream and the two that time the solve (read by cholmod_hip_get_stats)
-    double *d_sd_W = nullptr, *d_sd_acc = nullptr ; i64 sd_w_cap = 0 ;
+    double *d_sd_W = nullptr, *d_sd_acc = nullptr ;
     hipEvent_t sd_ev_in = nullptr, sd_ev0 = nullptr, sd_ev1 = nullptr ;
     bool sd_time_pending = false ;
     // progress of the running factorization, readable from another host thread (cholmod_hip_progress): the host side
@@ -380,6 +382,11 @@ struct cholmod_hip_plan {
     hipEvent_t ev0 = nullptr, ev1 = nullptr ;
     std::vector<hipEvent_t> evpool ;
 } ;
+
+// The complete numeric factor in the reference layout and the descriptors that go with it: the
+// rank's own array when there is one rank, the gathered copy otherwise (nullptr before a gather).
+static inline double *whole_factor (cholmod_hip_plan *P) { return P->world == 1 ? P->d_Lx : (P->full_valid ? P->d_Lx_full : nullptr) ; }
+static inline const FrontD *whole_fronts (cholmod_hip_plan *P) { return P->world == 1 ? P->d_fr : P->d_fr_full ; }
 
 namespace sship {
 
