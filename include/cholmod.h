@@ -395,6 +395,22 @@ int cholmod_l_hip_stats (cholmod_factor *L, double *stats, cholmod_common *Commo
  * zomplex L -- all checked before a device is touched.  nrhs == 0 is a success that touches nothing. */
 int cholmod_l_hip_solve_device (int sys, cholmod_factor *L, const double *B_dev, size_t ldb, double *X_dev, size_t ldx,
     size_t nrhs, void *stream, cholmod_common *Common) ;
+/* What follows a device solve, without leaving the device.  R_dev = B_dev - A X_dev (cholmod_l_hip_residual_device) and
+ * `steps` rounds of iterative refinement X_dev += (LL')^-1 (B_dev - A X_dev), in place (cholmod_l_hip_refine_device), in
+ * the caller's ordering.  "A" is the matrix L was last factorized from on the device, which is still resident there: A
+ * itself for a symmetric A, A*A' for stype == 0, A(:,f)*A(:,f)' with an fset, each plus beta*I with the beta of that
+ * factorization.  Arrays, leading dimensions and `stream` as for cholmod_l_hip_solve_device; X_dev and B_dev are read only
+ * by the residual, R_dev may be B_dev (same ld) but not X_dev.  Rnorm_dev: NULL, or nrhs doubles on the device that
+ * receive max_i |R (i,k)| (refine: of the final X; steps == 0 leaves X untouched and only reports them).  Two calls on the
+ * same inputs give bit-identical R and norms (cholmod_hip_residual_device in cholmod_hip.h).
+ * FALSE with CHOLMOD_INVALID for a NULL pointer, ld < n, steps < 0, R_dev == X_dev, a symbolic L, the GPU switched off
+ * (no host fallback: Common->hip_cpu_fallback does not apply; host arrays are cholmod_l_sdmult's) or an L that was not
+ * factorized on the device (no resident matrix); with CHOLMOD_NOT_INSTALLED for a complex or zomplex L -- all checked
+ * before a device is touched.  One rank only.  nrhs == 0 is a success that touches nothing. */
+int cholmod_l_hip_residual_device (cholmod_factor *L, const double *X_dev, size_t ldx, const double *B_dev, size_t ldb,
+    double *R_dev, size_t ldr, size_t nrhs, double *Rnorm_dev, void *stream, cholmod_common *Common) ;
+int cholmod_l_hip_refine_device (cholmod_factor *L, const double *B_dev, size_t ldb, double *X_dev, size_t ldx,
+    size_t nrhs, int steps, double *Rnorm_dev, void *stream, cholmod_common *Common) ;
 /* Where the relaxed fronts of an analysed L hold explicit zeros (cholmod_hip_plan_create_reach's reach_p / reach_first for
  * A's pattern and L's permutation): fills reach_p [0 .. nsuper] and, if reach_first is not NULL, reach_first; returns the
  * length of reach_first, -1 on invalid input.  cholmod_l_analyze computes the same for the plan it builds. */

@@ -285,6 +285,31 @@ int cholmod_hip_set_perm (cholmod_hip_plan *plan, const int64_t *Perm) ;
 int cholmod_hip_solve_device (cholmod_hip_plan *plan, int which, int perm_in, int perm_out,
     const double *dB, int64_t ldb, double *dX, int64_t ldx, int64_t nrhs, void *stream) ;
 
+/* (This entry point and the next: csrc/hip/residual.hip.)
+ * R = B - (A + beta I) X for the symmetric A whose permuted lower triangle is the resident S (cholmod_hip_upload_matrix,
+ * kept current by the value uploads) and the beta of the last factorization.  X, B, R: n-by-nrhs in device memory,
+ * column-major, leading dimensions ldx / ldb / ldr.  perm = 1: in the caller's ordering (rows gathered / scattered through
+ * Perm, cholmod_hip_set_perm first); perm = 0: in the factor's ordering (S itself).  dX, dB are read only; dR may be dB
+ * (same ld), must not be dX.  dRnorm: NULL, or nrhs doubles on the device that receive max_i |R (i,k)|.
+ * Every entry of R is summed by one owner in a fixed order and the norms go through an integer maximum: the same
+ * inputs give the same bits, call after call.  Fewer than 8 right-hand sides run column by column, 8 or more in panels of
+ * 16 (the layout of the solve above); any nrhs >= 0, nrhs == 0 or n == 0 is a success that touches nothing.
+ * The first call after a cholmod_hip_upload_matrix builds a transposed index of S's pattern (one download, a host pass,
+ * one upload: it waits for the engine stream) and the two further panels [n][16]; after that nothing is allocated, and the
+ * call is ordered on `stream` exactly as cholmod_hip_solve_device is (not during capture).
+ * CHOLMOD_HIP_INVALID, before any device call: NULL plan or pointers, a host-only plan, a plan of several ranks, ld < n,
+ * nrhs < 0, dR == dX, perm without a stored permutation, no resident S (a factor brought in by cholmod_hip_upload_factor
+ * only), the plans of complex factors (CHOLMOD_HIP_PHI_TWIN, CHOLMOD_HIP_CX_STORAGE). */
+int cholmod_hip_residual_device (cholmod_hip_plan *plan, int perm, const double *dX, int64_t ldx, const double *dB,
+    int64_t ldb, double *dR, int64_t ldr, int64_t nrhs, double *dRnorm, void *stream) ;
+
+/* `steps` rounds of  X += (LL')^-1 (B - (A + beta I) X)  in place on dX (perm as above), then the residual norms of
+ * the final X into dRnorm (NULL allowed).  steps == 0: X untouched, norms only.  The iteration stays in the factor's
+ * ordering: B and X pass through Perm once on the way in, X once on the way out.  Needs what the residual needs and,
+ * for steps > 0, the numeric factor as cholmod_hip_solve_device does; steps < 0 is CHOLMOD_HIP_INVALID. */
+int cholmod_hip_refine_device (cholmod_hip_plan *plan, int perm, const double *dB, int64_t ldb, double *dX, int64_t ldx,
+    int64_t nrhs, int steps, double *dRnorm, void *stream) ;
+
 /* Parity hooks: copy derived integer maps back to the host.
  *  sparent  [nsuper]     supernodal etree (reference :1025)
  *  level    [nsuper]     height of s in that tree (leaves 0)

@@ -142,7 +142,7 @@ API_SYMBOLS = [
     "cholmod_l_gpu_end", "cholmod_l_gpu_allocate",
     "cholmod_l_factor_to_host", "cholmod_l_hip_stats", "cholmod_l_refactorize_resident",
     "cholmod_l_gather_factor", "cholmod_l_hip_prepare", "cholmod_l_hip_front_reach",
-    "cholmod_l_hip_solve_device",
+    "cholmod_l_hip_solve_device", "cholmod_l_hip_residual_device", "cholmod_l_hip_refine_device",
 ]
 HIP_SYMBOLS = [
     "cholmod_hip_probe", "cholmod_hip_memorysize", "cholmod_hip_set_device", "cholmod_hip_device_count",
@@ -153,7 +153,7 @@ HIP_SYMBOLS = [
     "cholmod_hip_upload_matrix", "cholmod_hip_factorize_resident",
     "cholmod_hip_set_value_map",
     "cholmod_hip_download_factor", "cholmod_hip_download_even_columns", "cholmod_hip_upload_factor", "cholmod_hip_solve",
-    "cholmod_hip_set_perm", "cholmod_hip_solve_device",
+    "cholmod_hip_set_perm", "cholmod_hip_solve_device", "cholmod_hip_residual_device", "cholmod_hip_refine_device",
     "cholmod_hip_get_maps", "cholmod_hip_get_stats", "cholmod_hip_set_profiling",
     
     
@@ -284,6 +284,10 @@ def lib(hooks=None):
     sig("cholmod_hip_set_perm", C.c_int, [vp, vp])
     sig("cholmod_hip_solve_device", C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, vp])
     sig("cholmod_l_hip_solve_device", C.c_int, [C.c_int, fc, vp, sz, vp, sz, sz, vp, cm])
+    sig("cholmod_hip_residual_device", C.c_int, [vp, C.c_int, vp, i64, vp, i64, vp, i64, i64, vp, vp])
+    sig("cholmod_hip_refine_device", C.c_int, [vp, C.c_int, vp, i64, vp, i64, i64, C.c_int, vp, vp])
+    sig("cholmod_l_hip_residual_device", C.c_int, [fc, vp, sz, vp, sz, vp, sz, sz, vp, vp, cm])
+    sig("cholmod_l_hip_refine_device", C.c_int, [fc, vp, sz, vp, sz, sz, C.c_int, vp, vp, cm])
     sig("cholmod_hip_get_maps", C.c_int, [vp, vp, vp, vp])
     sig("cholmod_hip_get_stats", C.c_int, [vp, vp])
     sig("cholmod_hip_set_profiling", C.c_int, [vp, C.c_int])
@@ -468,6 +472,26 @@ class Session:
         self.free_dense(X)
         return out
 
+    @staticmethod
+    def _device_layout(what, n, t, like=None):
+        """(leading dimension, right-hand sides) of the column-major n-by-nrhs matrix the rows of the device tensor t
+        are: torch.float64, shape (nrhs, n) or (n,), unit stride along a row, any row stride >= n; `like`: a tensor
+        whose shape and device t must share."""
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64):
+            raise (TypeError if like is None else ValueError)(f"{what} must be a torch.float64 tensor on the device")
+        if t.dim() not in (1, 2) or t.shape[-1] != n:
+            raise ValueError(f"{what} must have shape (nrhs, {n}) or ({n},)")
+        if like is not None and (t.shape != like.shape or t.device != like.device):
+            raise ValueError(f"{what} must have the shape and the device of the other arrays")
+        if n > 1 and t.stride(-1) != 1:
+            raise ValueError(f"{what}: the entries of a right-hand side must be contiguous")
+        if t.dim() == 1 or t.shape[0] <= 1:
+            return n, (1 if t.dim() == 1 else int(t.shape[0]))
+        if t.stride(0) < n:
+            raise ValueError(f"{what}: row stride smaller than n")
+        return int(t.stride(0)), int(t.shape[0])
+
     def solve_device(self, Lf, B, sys=SYS_A, out=None):
         """cholmod_l_hip_solve_device: solve with right-hand sides that live on the device.  B: a torch.float64 device
         tensor of shape (nrhs, n) or (n,) -- rows are right-hand sides, as in `solve` -- with unit stride along a row
@@ -477,33 +501,55 @@ class Session:
         the two share one HIP runtime."""
         import torch
         n = int(Lf.contents.n)
-        if not (isinstance(B, torch.Tensor) and B.is_cuda and B.dtype == torch.float64):
-            raise TypeError("solve_device: B must be a torch.float64 tensor on the device")
-        if B.dim() not in (1, 2) or B.shape[-1] != n:
-            raise ValueError(f"solve_device: B must have shape (nrhs, {n}) or ({n},)")
+        ldb, nrhs = self._device_layout("solve_device: B", n, B)
         if out is None:
             out = torch.empty(B.shape, dtype=torch.float64, device=B.device)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64
-                  and out.shape == B.shape and out.device == B.device):
-            raise ValueError("solve_device: out must be a float64 device tensor of B's shape on B's device")
-
-        def layout(t):
-            # (leading dimension, right-hand sides) of the column-major n-by-nrhs matrix the rows of t are
-            if n > 1 and t.stride(-1) != 1:
-                raise ValueError("solve_device: the entries of a right-hand side must be contiguous")
-            if t.dim() == 1 or t.shape[0] <= 1:
-                return n, (1 if t.dim() == 1 else int(t.shape[0]))
-            if t.stride(0) < n:
-                raise ValueError("solve_device: row stride smaller than n")
-            return int(t.stride(0)), int(t.shape[0])
-
-        (ldb, nrhs), (ldx, _) = layout(B), layout(out)
+        ldx, _ = self._device_layout("solve_device: out", n, out, like=B)
         stream = torch.cuda.current_stream(B.device).cuda_stream
         ok = self.L.cholmod_l_hip_solve_device(sys, Lf, B.data_ptr() or 1, ldb, out.data_ptr() or 1, ldx, nrhs,
                                                stream, C.byref(self.cm))
         if not ok:
             raise RuntimeError(f"cholmod_l_hip_solve_device failed, status {self.cm.status}")
         return out
+
+    def residual_device(self, Lf, X, B, out=None, norms=False):
+        """cholmod_l_hip_residual_device: R = B - A X on the device, A being the matrix Lf was last factorized from
+        (plus beta I).  X, B: device tensors as for `solve_device`, of one shape.  Returns R as a new tensor or in `out`
+        (`out is B`: in place; never X); with norms=True, (R, norms): norms a device tensor of length nrhs holding
+        max |R| of every right-hand side.  Enqueued on torch's current stream; two calls on the same inputs give the same
+        bits."""
+        import torch
+        n = int(Lf.contents.n)
+        ldx, nrhs = self._device_layout("residual_device: X", n, X)
+        ldb, _ = self._device_layout("residual_device: B", n, B, like=X)
+        if out is None:
+            out = torch.empty(X.shape, dtype=torch.float64, device=X.device)
+        ldr, _ = self._device_layout("residual_device: out", n, out, like=X)
+        nrm = torch.empty(nrhs, dtype=torch.float64, device=X.device) if norms else None
+        stream = torch.cuda.current_stream(X.device).cuda_stream
+        # (empty tensors have no address: distinct stand-ins, R must not be X)
+        ok = self.L.cholmod_l_hip_residual_device(Lf, X.data_ptr() or 1, ldx, B.data_ptr() or 2, ldb, out.data_ptr() or 3,
+                                                  ldr, nrhs, nrm.data_ptr() if norms and nrhs else None, stream,
+                                                  C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_residual_device failed, status {self.cm.status}")
+        return (out, nrm) if norms else out
+
+    def refine_device(self, Lf, B, X, steps=1, norms=False):
+        """cholmod_l_hip_refine_device: `steps` rounds of X += A^-1 (B - A X) with the factor Lf, in place on the device
+        tensor X, which is returned; with norms=True, (X, norms): the residual norms of the final X (steps=0: X is left
+        alone and only its norms are formed).  Tensors and stream as for `residual_device`."""
+        import torch
+        n = int(Lf.contents.n)
+        ldb, nrhs = self._device_layout("refine_device: B", n, B)
+        ldx, _ = self._device_layout("refine_device: X", n, X, like=B)
+        nrm = torch.empty(nrhs, dtype=torch.float64, device=X.device) if norms else None
+        stream = torch.cuda.current_stream(X.device).cuda_stream
+        ok = self.L.cholmod_l_hip_refine_device(Lf, B.data_ptr() or 2, ldb, X.data_ptr() or 1, ldx, nrhs, int(steps),
+                                                nrm.data_ptr() if norms and nrhs else None, stream, C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_refine_device failed, status {self.cm.status}")
+        return (X, nrm) if norms else X
 
     def solve_subset(self, Lf, b, bset, sys=SYS_A, handles=None):
         """cholmod_l_solve2 with a sparse right-hand side: b (length n, only its entries at the indices `bset` are

@@ -69,14 +69,14 @@ static void free_device (cholmod_hip_plan *P)
         P->d_lvl_list, P->d_Lx, P->d_cb, P->d_zg, P->d_eg, P->d_pg, P->d_tg, P->d_tu_cnt, P->d_cdesc, P->d_smd, P->d_sp01, P->d_gg, P->d_sm,
         P->d_Sp, P->d_Si, P->d_Snz, P->d_Sx, P->d_amap, P->d_X, P->d_perm, P->d_xchg, P->d_stage, P->d_ag, P->d_agf, P->d_Lx_full, P->d_fr_full, P->d_dg, P->d_rg, P->d_wg, P->d_cg, P->d_cflags, P->d_crel, P->d_relpairs, P->d_dinv, P->d_sv,
         P->d_inv_tasks, P->d_winv, P->d_solved, P->d_sv_acc, P->d_sd_W, P->d_sd_acc, P->d_chk, P->d_chk_out, P->d_thin_tim, P->d_sb_tasks, P->d_sb_commit, P->d_first_fail, P->d_vsrc, P->d_vals,
-        P->d_xg, P->d_gmap} ;
+        P->d_xg, P->d_gmap, P->d_rs_Tp, P->d_rs_Tj, P->d_rs_Tq, P->d_rs_X, P->d_rs_B} ;
     for (void *p : ptrs) if (p) (void) hipFree (p) ;
     for (auto e : P->evpool) (void) hipEventDestroy (e) ;
     for (auto e : P->sync_ev) (void) hipEventDestroy (e) ;
     if (P->stream2) (void) hipStreamDestroy (P->stream2) ;
     if (P->ev0) (void) hipEventDestroy (P->ev0) ;
     if (P->ev1) (void) hipEventDestroy (P->ev1) ;
-    for (hipEvent_t e : {P->sd_ev_in, P->sd_ev0, P->sd_ev1}) if (e) (void) hipEventDestroy (e) ;
+    for (hipEvent_t e : {P->sd_ev_in, P->sd_ev0, P->sd_ev1, P->rs_ev_out}) if (e) (void) hipEventDestroy (e) ;
     if (P->stream) (void) hipStreamDestroy (P->stream) ;
 }
 
@@ -1434,6 +1434,7 @@ int cholmod_hip_upload_matrix (cholmod_hip_plan *P, const int64_t *Sp, const int
     HIPCHK (hipStreamSynchronize (P->stream)) ;
     P->s_unpacked = (Snz != nullptr) ;
     P->amap_valid = false ;         // a new pattern may have come with the new values
+    P->rs_index_valid = false ;     // ... and the transposed index of the residual goes with the old one
     P->s_cur_nz = nz ;
     P->vsrc_nz = 0 ;                // ... and the value map of the previous one is void
     P->h_vgather.clear () ; P->nchunks = 0 ;

@@ -1,7 +1,8 @@
 // plan.hip.h -- the types the host-side translation units of the engine share: the launch list (Launch, Schedule), the
 // contribution-block arena allocator, the RCCL entry points bound at run time, and the plan itself (cholmod_hip_plan:
 // one symbolic factor prepared for one rank).  plan_build.hip derives the plan (etree, ownership, layout, batches),
-// schedule_dense.hip the launches of a batch of fronts, engine.hip uploads and runs it, solve.hip solves with its factor.
+// schedule_dense.hip the launches of a batch of fronts, engine.hip uploads and runs it, solve.hip solves with its factor,
+// residual.hip forms residuals with its resident matrix.
 #pragma once
 #include "descriptors.hip.h"
 #include "../../../include/cholmod_hip.h"
@@ -369,6 +370,12 @@ struct cholmod_hip_plan {
     double *d_sd_W = nullptr, *d_sd_acc = nullptr ;
     hipEvent_t sd_ev_in = nullptr, sd_ev0 = nullptr, sd_ev1 = nullptr ;
     bool sd_time_pending = false ;
+    // device-resident residual and refinement (residual.hip): the transposed index of the resident S -- per row its
+    // entries left of the diagonal, column and position in d_Sx (built at the first call, void when S is uploaded anew)
+    // --, two more panels [n][16] for X and B in the factor's ordering, the event the caller's stream waits for
+    i64 *d_rs_Tp = nullptr, *d_rs_Tq = nullptr ; i32 *d_rs_Tj = nullptr ; bool rs_index_valid = false ;
+    double *d_rs_X = nullptr, *d_rs_B = nullptr ;
+    hipEvent_t rs_ev_out = nullptr ;
     // progress of the running factorization, readable from another host thread (cholmod_hip_progress): the host side
     // counts what it has enqueued; with markers enabled the device writes, in stream order, the sequence number of the
     // exchange it has entered / left into pinned host memory (prog_dev [0] / [1])

@@ -3,7 +3,7 @@
 // (plan_build.hip: sv_ptr, sb_launch, sb_commit_launch) through one driver, solve_sweeps; what differs is the kernel
 // family a step launches (solve_kernels.hip.h).  No test hook reaches this file: it is built once for both libraries.
 #include "solve_kernels.hip.h"
-#include "plan.hip.h"
+#include "solve_internal.hip.h"
 
 namespace {
 
@@ -165,9 +165,13 @@ static int solve_workspace (cholmod_hip_plan *P, i64 solved, i64 acc_nrhs, bool 
     return CHOLMOD_HIP_OK ;
 }
 
+} // namespace
+
+namespace sship {
+
 // the explicit inverses of the diagonal blocks of the big supernodes follow the factor: recomputed, on the engine
 // stream, by the first solve after it changed
-static void refresh_inverses (cholmod_hip_plan *P, const FrontD *frw, const double *Lw, bool cxs)
+void refresh_inverses (cholmod_hip_plan *P, const FrontD *frw, const double *Lw, bool cxs)
 {
     if (P->inv_tasks.empty () || P->winv_valid) return ;
     CXS_LAUNCH (k_diag_inv64, dim3 ((unsigned) P->inv_tasks.size ()), dim3 (64), 0, P->stream,
@@ -175,7 +179,7 @@ static void refresh_inverses (cholmod_hip_plan *P, const FrontD *frw, const doub
     P->winv_valid = true ;
 }
 
-} // namespace
+} // namespace sship
 
 int cholmod_hip_solve (cholmod_hip_plan *P, int which, double *X, int64_t nrhs, int64_t ldx)
 {
@@ -234,14 +238,10 @@ int cholmod_hip_set_perm (cholmod_hip_plan *P, const int64_t *Perm)
     return CHOLMOD_HIP_OK ;
 }
 
-// first nrhs that takes the 16-wide kernels.  A panel costs what about 3.5 sweeps of the one-column kernels cost
-// (Poisson 100^3: 31 ms against 9.2 ms; its walk over the big supernodes is as latency-bound as theirs), and they
-// take about 4.6 ms per further column: the panel wins from 6 - 8 right-hand sides on the 3D problems, from 4 on
-// the 2D one (profiles/solve_device_times.json).  Below it the right-hand sides run column by column.
-#define SD_BLOCK_MIN_NRHS 8
+namespace sship {
 
 // workspaces of a device-resident solve; nothing is allocated once they exist
-static int sd_ensure (cholmod_hip_plan *P, bool with_factor, bool columns)
+int sd_ensure (cholmod_hip_plan *P, bool with_factor, bool columns)
 {
     const i64 n = P->n ;
     if (!P->sd_ev_in)
@@ -259,7 +259,7 @@ static int sd_ensure (cholmod_hip_plan *P, bool with_factor, bool columns)
 }
 
 // the columns src [nrhs][lds] into dst [nrhs][ldd], through the permutation if there is one (inverse: scattered by it)
-static int sd_move_columns (hipStream_t st, i64 n, i64 nrhs, const i64 *perm, int inverse, const double *src, i64 lds, double *dst, i64 ldd)
+int sd_move_columns (hipStream_t st, i64 n, i64 nrhs, const i64 *perm, int inverse, const double *src, i64 lds, double *dst, i64 ldd)
 {
     if (perm) for (i64 r = 0 ; r < nrhs ; r++)
         hipLaunchKernelGGL (k_perm, dim3 ((unsigned) ((n + 255) / 256)), dim3 (256), 0, st, n, perm, src + r * lds, dst + r * ldd, inverse) ;
@@ -267,6 +267,28 @@ static int sd_move_columns (hipStream_t st, i64 n, i64 nrhs, const i64 *perm, in
         hipMemcpyDeviceToDevice, st)) ;
     return CHOLMOD_HIP_OK ;
 }
+
+void sd_pack (hipStream_t st, i64 n, const i64 *perm, const double *B, i64 ldb, int pw, double *W)
+{
+    hipLaunchKernelGGL (k_sd_pack, dim3 ((unsigned) ((n + 255) / 256)), dim3 (256), 0, st, n, perm, B, ldb, pw, W) ;
+}
+
+void sd_unpack (hipStream_t st, i64 n, const i64 *perm, const double *W, int pw, double *X, i64 ldx)
+{
+    hipLaunchKernelGGL (k_sd_unpack, dim3 ((unsigned) ((n + 255) / 256)), dim3 (256), 0, st, n, perm, W, pw, X, ldx) ;
+}
+
+void sd_sweeps_columns (const cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, hipStream_t st, double *x, i64 ldx, int nrhs)
+{
+    solve_sweeps (P, which, ColumnKernels {P, frw, Lw, st, x, ldx, nrhs, false}) ;
+}
+
+void sd_sweeps_panel (const cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, hipStream_t st, double *W)
+{
+    solve_sweeps (P, which, PanelKernels {P, frw, Lw, st, W}) ;
+}
+
+} // namespace sship
 
 int cholmod_hip_solve_device (cholmod_hip_plan *P, int which, int perm_in, int perm_out, const double *dB, int64_t ldb,
     double *dX, int64_t ldx, int64_t nrhs, void *stream)

@@ -962,6 +962,75 @@ int cholmod_l_hip_solve_device (int sys, cholmod_factor *L, const double *B_dev,
     return (rc == CHOLMOD_HIP_OK) ? TRUE : map_hip_status (rc, Common, "HIP device solve failed") ;
 }
 
+/* what cholmod_l_hip_residual_device and cholmod_l_hip_refine_device check alike, in the order of the solve above; then
+ * the permutation goes to the plan.  TRUE: *plan is ready (NULL: nothing to do). */
+static int residual_ready (cholmod_factor *L, size_t ld1, size_t ld2, size_t ld3, size_t nrhs, cholmod_hip_plan **plan,
+    cholmod_common *Common)
+{
+    *plan = NULL ;
+    if (ld1 < L->n || ld2 < L->n || ld3 < L->n) { ERROR (CHOLMOD_INVALID, "leading dimension smaller than n") ; return FALSE ; }
+    if (L->xtype == CHOLMOD_COMPLEX || L->xtype == CHOLMOD_ZOMPLEX)
+    { ERROR (CHOLMOD_NOT_INSTALLED, "a device residual with a complex factor is not supported") ; return FALSE ; }
+    if (L->xtype != CHOLMOD_REAL || !L->is_super)
+    { ERROR (CHOLMOD_INVALID, "L must be a numeric supernodal factor") ; return FALSE ; }
+    if (ssamd_resolve_use_gpu (Common) != 1) { ERROR (CHOLMOD_INVALID, "a device residual needs Common->useGPU") ; return FALSE ; }
+    if (Common->hip_world > 1) { ERROR (CHOLMOD_INVALID, "the device residual runs on one rank only") ; return FALSE ; }
+    if (!L->hip_plan || !L->hip_on_device)
+    { ERROR (CHOLMOD_INVALID, "no resident matrix: L was not factorized on the device") ; return FALSE ; }
+    Common->status = CHOLMOD_OK ;
+    if (nrhs == 0 || L->n == 0) return TRUE ;
+    if (!L->hip_perm_set)
+    {
+        int rc = cholmod_hip_set_perm ((cholmod_hip_plan *) L->hip_plan, (const int64_t *) L->Perm) ;
+        if (rc != CHOLMOD_HIP_OK) return map_hip_status (rc, Common, "the permutation could not be stored on the device") ;
+        L->hip_perm_set = TRUE ;
+    }
+    *plan = (cholmod_hip_plan *) L->hip_plan ;
+    return TRUE ;
+}
+
+/* (everything else that is invalid has been checked above: what the engine still refuses is a plan without a matrix) */
+static int residual_status (int rc, cholmod_common *Common, const char *what)
+{
+    if (rc == CHOLMOD_HIP_OK) return TRUE ;
+    if (rc == CHOLMOD_HIP_INVALID)
+    { ERROR (CHOLMOD_INVALID, "no resident matrix: the plan holds a factor that was not computed from a matrix on the device") ; return FALSE ; }
+    return map_hip_status (rc, Common, what) ;
+}
+
+/* R = B - A X with all three in device memory, A the matrix L was last factorized from on the device (cholmod.h) */
+int cholmod_l_hip_residual_device (cholmod_factor *L, const double *X_dev, size_t ldx, const double *B_dev, size_t ldb,
+    double *R_dev, size_t ldr, size_t nrhs, double *Rnorm_dev, void *stream, cholmod_common *Common)
+{
+    RETURN_IF_NULL_COMMON (FALSE) ;
+    RETURN_IF_NULL (L, FALSE) ;
+    RETURN_IF_NULL (X_dev, FALSE) ;
+    RETURN_IF_NULL (B_dev, FALSE) ;
+    RETURN_IF_NULL (R_dev, FALSE) ;
+    if (R_dev == X_dev) { ERROR (CHOLMOD_INVALID, "R must not be X") ; return FALSE ; }
+    cholmod_hip_plan *plan ;
+    if (!residual_ready (L, ldx, ldb, ldr, nrhs, &plan, Common)) return FALSE ;
+    if (!plan) return TRUE ;
+    return residual_status (cholmod_hip_residual_device (plan, 1, X_dev, (int64_t) ldx, B_dev, (int64_t) ldb, R_dev,
+        (int64_t) ldr, (int64_t) nrhs, Rnorm_dev, stream), Common, "HIP device residual failed") ;
+}
+
+/* `steps` rounds of iterative refinement of X against B, in place in device memory (cholmod.h) */
+int cholmod_l_hip_refine_device (cholmod_factor *L, const double *B_dev, size_t ldb, double *X_dev, size_t ldx,
+    size_t nrhs, int steps, double *Rnorm_dev, void *stream, cholmod_common *Common)
+{
+    RETURN_IF_NULL_COMMON (FALSE) ;
+    RETURN_IF_NULL (L, FALSE) ;
+    RETURN_IF_NULL (B_dev, FALSE) ;
+    RETURN_IF_NULL (X_dev, FALSE) ;
+    if (steps < 0) { ERROR (CHOLMOD_INVALID, "steps must not be negative") ; return FALSE ; }
+    cholmod_hip_plan *plan ;
+    if (!residual_ready (L, ldb, ldx, ldx, nrhs, &plan, Common)) return FALSE ;
+    if (!plan) return TRUE ;
+    return residual_status (cholmod_hip_refine_device (plan, 1, B_dev, (int64_t) ldb, X_dev, (int64_t) ldx, (int64_t) nrhs,
+        steps, Rnorm_dev, stream), Common, "HIP device refinement failed") ;
+}
+
 /* the triangular solves run where the factor is: on the host when the values are
  * in L->x and the engine is not to be used (Common->useGPU == 0, no device, or a
  * factor the CPU path computed) */
