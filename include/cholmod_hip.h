@@ -319,16 +319,20 @@ int cholmod_hip_get_maps (cholmod_hip_plan *plan, int64_t *sparent,
     int64_t *level, int64_t *relmap) ;
 
 /* out3 = {min L_jj, max L_jj, number of NaN or negative diagonal entries} of the resident factor (one pass over the n
- * diagonal entries on the device): what cholmod_l_rcond needs (CHOLMOD/Cholesky/cholmod_rcond.c:64-161).  Several ranks:
- * after cholmod_hip_gather_factor. */
+ * diagonal entries on the device): what cholmod_l_rcond needs (CHOLMOD/Cholesky/cholmod_rcond.c:64-161).  The extremes
+ * are taken over the entries >= 0 only (+inf and 0 if there is none) and are those entries bit for bit, except that a zero
+ * diagonal entry of either sign gives the minimum +0.0 (-0.0 is not a negative entry).  Several ranks: after
+ * cholmod_hip_gather_factor. */
 int cholmod_hip_diag_minmax (cholmod_hip_plan *plan, double *out3) ;
 /* Size-independent invariants of the device-resident factor, one pass over Lx
  * (the checks CHOLMOD/Check/cholmod_check.c:1823-2000 cannot do on values, at
  * sizes no CPU oracle reaches):  out5[0] = sum_j log L(j,j)  (= logdet(A)/2,
  * known in closed form for the Poisson grids);  out5[1] = entries != 0 in the
- * dead strictly-upper triangles of the diagonal blocks;  out5[2] = non-finite
- * entries of the lower trapezoids;  out5[3] = ||L||_F^2 over the lower
- * trapezoids;  out5[4] = diagonal entries <= 0. */
+ * dead strictly-upper triangles of the diagonal blocks (a NaN counts, -0.0
+ * does not);  out5[2] = non-finite entries of the lower trapezoids;
+ * out5[3] = ||L||_F^2 over the finite entries of the lower trapezoids;
+ * out5[4] = diagonal entries that are not > 0: zero of either sign, negative
+ * or NaN (out5[0] sums over the others only). */
 int cholmod_hip_factor_checks (cholmod_hip_plan *plan, double *out5) ;
 /* The same five numbers over the fronts this rank answers for (the first rank of a front's group),
  * from the rank's own part of a distributed factor: their sums over the ranks are the invariants

@@ -280,6 +280,8 @@ def lib(hooks=None):
     sig("cholmod_hip_factorize_resident", C.c_int, [vp, dbl, C.c_int, C.POINTER(i64)])
     sig("cholmod_hip_download_factor", C.c_int, [vp, vp])
     sig("cholmod_hip_upload_factor", C.c_int, [vp, vp])
+    sig("cholmod_hip_download_even_columns", C.c_int, [vp, vp])
+    sig("cholmod_hip_diag_minmax", C.c_int, [vp, vp])
     sig("cholmod_hip_solve", C.c_int, [vp, C.c_int, vp, i64, i64])
     sig("cholmod_hip_set_perm", C.c_int, [vp, vp])
     sig("cholmod_hip_solve_device", C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, vp])

@@ -3085,7 +3085,8 @@ __global__ void __launch_bounds__(256) k_chainf (const CfGroup *g, int ng, int n
 
 // ---- extreme diagonal entries of L (cholmod_l_rcond on a device-resident factor) ---------------------
 // out [0] = min L_jj, out [1] = max L_jj (as ordered bit patterns of NON-NEGATIVE doubles: the caller seeds them with
-// +inf / 0), out [2] += number of NaN or negative diagonal entries.  One thread per column; CX: a complex factor in its own
+// +inf / 0), out [2] += number of NaN or negative diagonal entries; a diagonal entry -0.0 counts as +0.0 (a minimum of 0,
+// not a negative entry).  One thread per column; CX: a complex factor in its own
 // storage, the diagonal of the complex L is the (real) entry (2j, 2j) of the twin, kept in the even column 2j.
 template <bool CX>
 __global__ void __launch_bounds__(256) k_diag_minmax (i64 n, const i32 *supermap, const FrontD *fr, const double *Lx, unsigned long long *out)
@@ -3100,6 +3101,10 @@ __global__ void __launch_bounds__(256) k_diag_minmax (i64 n, const i32 *supermap
         v = Lx [f.psx + jj + colx<CX> (jj, f.nsrow)] ;
         have = true ;
         if (!(v >= 0.0)) { bad = true ; have = false ; }        // (NaN or negative: counted, kept out of the extremes)
+        // a zero of either sign is the minimum +0.0: the bit pattern of -0.0 is above that of +inf as an unsigned integer,
+        // so it would win the wave's comparisons and then lose the atomicMin, and the wave's minimum with it
+        // (-0.0 + 0.0 = +0.0 in round-to-nearest, every other value unchanged; needs signed zeros, i.e. no fast-math build)
+        v = v + 0.0 ;
     }
     double lo = have ? v : __builtin_inf (), hi = have ? v : 0.0 ;
     for (int o = 32 ; o > 0 ; o >>= 1)
@@ -3130,10 +3135,11 @@ __global__ void __launch_bounds__(256) k_first_fail (i64 nsuper, const i32 *info
 // One pass over Lx (parity checks at sizes the CPU oracle cannot reach):
 //   out[0] += sum_j log L(j,j)          (= logdet(A)/2, analytic for Poisson grids)
 //   out[1] += entries != 0 in the dead strictly-upper triangles of the diagonal
-//             blocks (the reference never writes them)
+//             blocks (the reference never writes them);
+//             a NaN counts, -0.0 does not
 //   out[2] += non-finite entries of the lower trapezoids
-//   out[3] += sum of squares of the lower trapezoids (||L||_F^2)
-//   out[4] += diagonal entries <= 0
+//   out[3] += sum of squares of the finite entries of the lower trapezoids (||L||_F^2)
+//   out[4] += diagonal entries that are not > 0 (zero of either sign, negative, NaN)
 // A workgroup owns CHK_COLS columns of one supernode; wave w takes the columns
 // == w (mod 4), lanes stride the rows (coalesced).
 // ---- even columns of the factor (complex input through the real embedding) ---------
