@@ -198,7 +198,24 @@ int cholmod_hip_gather_factor (cholmod_hip_plan *plan) ;
  * The factor stays resident in HBM; if Lx_host != NULL the packed Lx array
  * (xsize doubles, reference layout) is also copied back.
  * *minor receives L->minor (== n when positive definite).
- * Returns CHOLMOD_HIP_OK, CHOLMOD_HIP_NOT_POSDEF, or a negative error. */
+ * Returns CHOLMOD_HIP_OK, CHOLMOD_HIP_NOT_POSDEF, or a negative error.
+ *
+ * Supported pivot range (this entry point, cholmod_hip_factorize_resident and
+ * cholmod_hip_dense_partial_factor).  A pivot is the diagonal entry as the elimination
+ * reaches it.
+ *  - Any normal double, DBL_MIN .. DBL_MAX: L(j,j) is within 1 ulp of sqrt (pivot); the
+ *    kernels rescale by 2^+-512 outside [1e-290, 1e290], nothing else depends on the
+ *    magnitude.  The factorization commutes with a scaling D A D by powers of two
+ *    (L becomes D L, to rounding) as long as the entries of D A D and of D L stay normal
+ *    doubles and max |A| < 2^1020: the columns are eliminated unscaled (an LDL' step with
+ *    1 / pivot), so the entries of A, not only of L, must leave that room.
+ *  - pivot <= 0 -- +0.0, -0.0, any negative value down to -5e-324 -- is a failure at
+ *    that column (LAPACK's ajj <= 0): *minor / info name it, the columns from it on are
+ *    zero.  NaN pivots do not stop the factorization.
+ *  - A positive subnormal pivot (5e-324 .. DBL_MIN) is not a failure either.  Its square
+ *    root takes the same rescaled sequence (no accuracy is promised for it; the tests
+ *    measure it), but 1 / pivot overflows: the entries below it in its column are not
+ *    finite unless the column has none (a 1 x 1 front, a last column).  Not supported. */
 int cholmod_hip_factorize (cholmod_hip_plan *plan, const int64_t *Sp,
     const int64_t *Si, const int64_t *Snz, const double *Sx, double beta,
     int quick_return_if_not_posdef, double *Lx_host, int64_t *minor) ;
