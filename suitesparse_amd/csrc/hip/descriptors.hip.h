@@ -120,7 +120,7 @@ struct RelPair { i32 d ; i32 a ; i64 off ; } ;
 // thin fronts (k_thin_front): most rows, panel width
 #define SM_MAX 136
 #define TF_PW 16
-// the exchange of a block column of a shared front (k_xchg_move; see kernels.hip.h)
+// the exchange of a block column of a shared front (k_xchg_move; see exchange_kernels.hip.h)
 struct XchgD {
     i64 slab ;      // offset in Lx of entry (b0, b0) of the front
     i32 lda ;       // nsrow

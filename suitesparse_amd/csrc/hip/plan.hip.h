@@ -1,8 +1,8 @@
 // plan.hip.h -- the types the host-side translation units of the engine share: the launch list (Launch, Schedule), the
 // contribution-block arena allocator, the RCCL entry points bound at run time, and the plan itself (cholmod_hip_plan:
 // one symbolic factor prepared for one rank).  plan_build.hip derives the plan (etree, ownership, layout, batches),
-// schedule_dense.hip the launches of a batch of fronts, engine.hip uploads and runs it, solve.hip solves with its factor,
-// residual.hip forms residuals with its resident matrix.
+// schedule_dense.hip the launches of a batch of fronts, engine.hip uploads and runs it, exchange.hip moves what its ranks
+// share, solve.hip solves with its factor, residual.hip forms residuals with its resident matrix.
 #pragma once
 #include "descriptors.hip.h"
 #include "../../../include/cholmod_hip.h"
@@ -217,7 +217,7 @@ struct RcclApi {
     ncclResult_t (*CommDestroy) (ncclComm_t) = nullptr ;
     const char *(*GetErrorString) (ncclResult_t) = nullptr ;
 } ;
-RcclApi *rccl_api () ;      // (engine.hip)
+RcclApi *rccl_api () ;      // (exchange.hip)
 
 } // namespace sship
 

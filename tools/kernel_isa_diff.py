@@ -2,9 +2,9 @@
 """Is a restructuring of the HIP sources neutral for the device code?  Compares, kernel by kernel, the gfx950 assembly of
 two builds:
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -save-temps=obj -c hip/engine.hip -o OLD/engine.o     (the old tree)
-    ... the same for every device translation unit of the new tree (engine.hip, solve.hip) into NEW/
-    python tools/kernel_isa_diff.py OLD/engine-hip-amdgcn-amd-amdhsa-gfx950.s NEW/*-hip-amdgcn-amd-amdhsa-gfx950.s
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -save-temps=obj -c hip/UNIT.hip -o OLD/UNIT.o     (the old tree)
+    ... the same for every translation unit of the new tree that now holds some of UNIT's kernels, into NEW/
+    python tools/kernel_isa_diff.py OLD/UNIT-hip-amdgcn-amd-amdhsa-gfx950.s NEW/*-hip-amdgcn-amd-amdhsa-gfx950.s
 
 Every kernel of the first file must be in exactly one of the others with the same instruction text and the same
 .amdhsa_kernel block (registers, LDS, scratch), and the same resources in the metadata; the others may hold no kernel
