@@ -262,6 +262,11 @@ typedef struct cholmod_factor_struct
     void *bset_work ;           /* cholmod_l_solve2 with Bset: column -> supernode, flags (2n + 1 integers, built by the first call) */
     int hip_plan_ahead ;        /* != 0: hip_plan was built inside cholmod_l_analyze and no factorization has used it yet (plan flags + 1) */
     int hip_perm_set ;          /* hip_plan holds L->Perm (cholmod_l_hip_solve_device hands it over on first use) */
+    /* cholmod_l_hip_factorize_values_device with an unsymmetric A (stype 0): hip_apat_hash is then the hash of tril (A*A')'s
+     * pattern; once A's product map is on the plan these hold the hash of A's OWN pattern, all a later call pays for */
+    uint64_t hip_aat_hash, hip_aat_hash2 ;
+    size_t hip_aat_nnz ;
+    int hip_aat_valid ;
 } cholmod_factor ;
 
 /* ---- Core ---------------------------------------------------------------- */
@@ -411,6 +416,35 @@ int cholmod_l_hip_residual_device (cholmod_factor *L, const double *X_dev, size_
     double *R_dev, size_t ldr, size_t nrhs, double *Rnorm_dev, void *stream, cholmod_common *Common) ;
 int cholmod_l_hip_refine_device (cholmod_factor *L, const double *B_dev, size_t ldb, double *X_dev, size_t ldx,
     size_t nrhs, int steps, double *Rnorm_dev, void *stream, cholmod_common *Common) ;
+/* cholmod_l_factorize for new VALUES of A that already live in device memory (a matrix assembled on the GPU: the step of a
+ * Newton, time-stepping or interior-point loop), without a trip through the host.  A supplies the PATTERN only (p, i,
+ * stype, packed; A->x is never read and may be NULL); Ax_dev is a device pointer to nnz (A) doubles in A's own entry
+ * order, read only; `stream` is the caller's hipStream_t (NULL: the null stream), and the call takes its place on it as
+ * cholmod_l_hip_solve_device does: behind what the caller has enqueued (the kernels that produce Ax_dev), ahead of what it
+ * enqueues next (not during stream capture).
+ * PRECONDITION: L was last factorized on the device by cholmod_l_factorize (_p) from a HOST matrix of this pattern, without
+ * an fset -- that call left the plan, the resident matrix, its value map and the pattern hash.  The call hashes A's
+ * pattern as the values-only path of cholmod_l_factorize does; on a mismatch it returns FALSE with CHOLMOD_INVALID,
+ * touches no device state and L keeps its factor.
+ * stype == 0: L L' = A*A' + beta*I.  The resident matrix is tril (A*A') and its values are formed on the device from
+ * Ax_dev (cholmod_hip_set_product_map); the first such call forms the pattern of A*A' symbolically, checks its hash and
+ * builds the product map (cholmod_l_hip_aat_product_map) -- a host pass and 16 bytes of HBM per pair that a caller who
+ * never uses this entry does not pay --, later calls hash A only.
+ * THE CALL RETURNS WHEN THE FACTORIZATION HAS FINISHED ON THE DEVICE, with the result of cholmod_l_factorize: L->minor is
+ * set, CHOLMOD_NOT_POSDEF is a warning status with TRUE, the host copy L->x is stale (cholmod_l_factor_to_host; with
+ * Common->hip_factor_on_device off it is downloaded as usual).  Ax_dev may be overwritten once the call has returned.
+ * The host values-only path keeps working afterwards, and the device solve, residual and refinement see the new matrix.
+ * FALSE with CHOLMOD_INVALID for NULL pointers, an unpacked A, mismatched dimensions, a symbolic L, an L without the
+ * pattern record (L->hip_apat_valid unset), several ranks, the GPU switched off (no host fallback for device pointers:
+ * Common->hip_cpu_fallback does not apply); with CHOLMOD_NOT_INSTALLED for a complex or zomplex A or L -- all checked
+ * before a device is touched. */
+int cholmod_l_hip_factorize_values_device (cholmod_sparse *A, const double *Ax_dev, double beta [2],
+    cholmod_factor *L, void *stream, cholmod_common *Common) ;
+/* The values of C = tril (A*A') as sums of products of the values of an unsymmetric A (stype 0): entry c of C, in the
+ * entry order of the lower triangle by sorted columns, is sum over p = cp [c] .. cp [c+1]-1 of Ax [ia [p]] * Ax [ib [p]],
+ * the pairs of a list by ascending column of A.  Pure integer work on the host; returns the number of pairs, -1 on invalid
+ * input; cp [0 .. nnz (C)], ia, ib are filled where they are not NULL (all NULL: the count only). */
+int64_t cholmod_l_hip_aat_product_map (cholmod_sparse *A, int64_t *cp, int64_t *ia, int64_t *ib, cholmod_common *Common) ;
 /* Where the relaxed fronts of an analysed L hold explicit zeros (cholmod_hip_plan_create_reach's reach_p / reach_first for
  * A's pattern and L's permutation): fills reach_p [0 .. nsuper] and, if reach_first is not NULL, reach_first; returns the
  * length of reach_first, -1 on invalid input.  cholmod_l_analyze computes the same for the plan it builds. */

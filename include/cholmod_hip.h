@@ -249,6 +249,41 @@ int cholmod_hip_values_begin (cholmod_hip_plan *plan, double **buffer, const int
     int64_t *count, int64_t *chunk_len) ;
 int cholmod_hip_values_push_chunk (cholmod_hip_plan *plan, int64_t chunk) ;
 
+/* The same values-only factorization for values that already live in device memory (a matrix assembled on the GPU):
+ * dvalues is a DEVICE pointer to the caller's value array, nvalues doubles in the order cholmod_hip_set_value_map was
+ * given for, read only.  The engine stream waits for an event recorded on `stream` (the caller's hipStream_t, NULL: the
+ * null stream), exactly as cholmod_hip_solve_device does; the values are gathered from dvalues straight into the resident
+ * S -- no copy into the plan's value buffer, no pinned staging, nothing crosses PCIe -- and the factorization runs as
+ * cholmod_hip_factorize_resident runs it on a resident S with a valid assembly map: every entry of L receives exactly one
+ * value of S.  PRECONDITION: a resident packed S with its value map (cholmod_hip_upload_matrix, a factorization,
+ * cholmod_hip_set_value_map): the first factorization of a pattern still comes from the host.
+ * THE CALL RETURNS WHEN THE FACTORIZATION HAS FINISHED ON THE DEVICE: it reports *minor and CHOLMOD_HIP_NOT_POSDEF as
+ * cholmod_hip_factorize_resident does.  `stream` then waits for the engine's completion event, so later work on it (a
+ * cholmod_hip_solve_device, say) needs no host synchronisation, and dvalues may be overwritten once the call has
+ * returned.  The resident S is current afterwards: cholmod_hip_residual_device / _refine_device use the new matrix.
+ * CHOLMOD_HIP_INVALID, before any device call: a NULL plan or pointer, a host-only plan, a plan of several ranks, no value
+ * map for the current resident S, nvalues other than the value map's nvalues (the product map's navalues when one is
+ * set), a host upload under way (cholmod_hip_values_begin without its factorization), the plans of complex factors
+ * (CHOLMOD_HIP_PHI_TWIN, CHOLMOD_HIP_CX_STORAGE).  Must not be called while `stream` is being captured into a graph. */
+int cholmod_hip_factorize_values_device (cholmod_hip_plan *plan, const double *dvalues, int64_t nvalues,
+    double beta, int quick_return_if_not_posdef, void *stream, int64_t *minor) ;
+
+/* The nc = nvalues values of the value map are then not given but COMPUTED on the device: value c is
+ *     sum over p = cp [c] .. cp [c+1]-1 of a [ia [p]] * a [ib [p]]
+ * over the navalues values a of the array cholmod_hip_factorize_values_device is then passed (S = tril (A A') from the
+ * values of A: the normal equations).  The sums are formed into the plan's own value buffer on the engine stream and
+ * gathered into S from there; each is added up by one owner in an order that depends on its list alone, without
+ * floating-point atomics: the same values give the same bits.  Every index is validated here, on the host
+ * (0 <= ia, ib < navalues, cp [0] == 0 and monotone, nc equal to the value map's nvalues: anything else is
+ * CHOLMOD_HIP_INVALID), so the kernel reads nothing outside a [0 .. navalues); more than INT32_MAX pairs or values is
+ * CHOLMOD_HIP_TOO_LARGE.  The map costs 16 bytes of HBM per pair.  cholmod_hip_set_value_map and
+ * cholmod_hip_upload_matrix drop it; so does cp == NULL.  The host value upload above is not affected by it. */
+int cholmod_hip_set_product_map (cholmod_hip_plan *plan, const int64_t *cp, const int64_t *ia, const int64_t *ib,
+    int64_t nc, int64_t navalues) ;
+
+/* The values of the resident S (snz doubles, the order of the uploaded pattern) to the host; waits for the engine stream. */
+int cholmod_hip_download_matrix_values (cholmod_hip_plan *plan, double *Sx_host) ;
+
 /* Copy the device-resident packed Lx (xsize doubles) to the host. */
 int cholmod_hip_download_factor (cholmod_hip_plan *plan, double *Lx_host) ;
 /* Even columns only, packed (xsize / 2 doubles): for a plan built on the doubled

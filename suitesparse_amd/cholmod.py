@@ -116,7 +116,9 @@ class Factor(C.Structure):
                 ("hip_plan", C.c_void_p), ("hip_on_device", C.c_int), ("hip_host_valid", C.c_int),
                 ("cx_twin", C.c_void_p), ("hip_apat_hash", C.c_uint64), ("hip_apat_nnz", C.c_size_t),
                 ("hip_apat_valid", C.c_int), ("hip_apat_hash2", C.c_uint64), ("hip_is_twin", C.c_int),
-                ("bset_work", C.c_void_p), ("hip_plan_ahead", C.c_int), ("hip_perm_set", C.c_int)]
+                ("bset_work", C.c_void_p), ("hip_plan_ahead", C.c_int), ("hip_perm_set", C.c_int),
+                ("hip_aat_hash", C.c_uint64), ("hip_aat_hash2", C.c_uint64), ("hip_aat_nnz", C.c_size_t),
+                ("hip_aat_valid", C.c_int)]
 
 
 # every symbol include/cholmod.h and include/cholmod_hip.h declare
@@ -143,6 +145,7 @@ API_SYMBOLS = [
     "cholmod_l_factor_to_host", "cholmod_l_hip_stats", "cholmod_l_refactorize_resident",
     "cholmod_l_gather_factor", "cholmod_l_hip_prepare", "cholmod_l_hip_front_reach",
     "cholmod_l_hip_solve_device", "cholmod_l_hip_residual_device", "cholmod_l_hip_refine_device",
+    "cholmod_l_hip_factorize_values_device", "cholmod_l_hip_aat_product_map",
 ]
 HIP_SYMBOLS = [
     "cholmod_hip_probe", "cholmod_hip_memorysize", "cholmod_hip_set_device", "cholmod_hip_device_count",
@@ -152,6 +155,7 @@ HIP_SYMBOLS = [
     "cholmod_hip_gather_factor",
     "cholmod_hip_upload_matrix", "cholmod_hip_factorize_resident",
     "cholmod_hip_set_value_map",
+    "cholmod_hip_factorize_values_device", "cholmod_hip_set_product_map", "cholmod_hip_download_matrix_values",
     "cholmod_hip_download_factor", "cholmod_hip_download_even_columns", "cholmod_hip_upload_factor", "cholmod_hip_solve",
     "cholmod_hip_set_perm", "cholmod_hip_solve_device", "cholmod_hip_residual_device", "cholmod_hip_refine_device",
     "cholmod_hip_get_maps", "cholmod_hip_get_stats", "cholmod_hip_set_profiling",
@@ -290,6 +294,11 @@ def lib(hooks=None):
     sig("cholmod_hip_refine_device", C.c_int, [vp, C.c_int, vp, i64, vp, i64, i64, C.c_int, vp, vp])
     sig("cholmod_l_hip_residual_device", C.c_int, [fc, vp, sz, vp, sz, vp, sz, sz, vp, vp, cm])
     sig("cholmod_l_hip_refine_device", C.c_int, [fc, vp, sz, vp, sz, sz, C.c_int, vp, vp, cm])
+    sig("cholmod_hip_factorize_values_device", C.c_int, [vp, vp, i64, dbl, C.c_int, vp, C.POINTER(i64)])
+    sig("cholmod_hip_set_product_map", C.c_int, [vp, vp, vp, vp, i64, i64])
+    sig("cholmod_hip_download_matrix_values", C.c_int, [vp, vp])
+    sig("cholmod_l_hip_factorize_values_device", C.c_int, [sp, vp, C.POINTER(dbl * 2), fc, vp, cm])
+    sig("cholmod_l_hip_aat_product_map", i64, [sp, vp, vp, vp, cm])
     sig("cholmod_hip_get_maps", C.c_int, [vp, vp, vp, vp])
     sig("cholmod_hip_get_stats", C.c_int, [vp, vp])
     sig("cholmod_hip_set_profiling", C.c_int, [vp, C.c_int])
@@ -459,6 +468,23 @@ class Session:
     def factorize(self, A, Lf, beta=0.0):
         b = (C.c_double * 2)(beta, 0.0)
         return self.L.cholmod_l_factorize_p(A, C.byref(b), None, 0, Lf, C.byref(self.cm))
+
+    def factorize_device(self, A, values, Lf, beta=0.0):
+        """cholmod_l_hip_factorize_values_device: `factorize` for new values of A that live on the device.  A gives the
+        pattern (its host values are not read); values: a 1-D contiguous torch.float64 device tensor of length nnz (A), in
+        A's entry order.  Lf must have been factorized from a host matrix of this pattern before.  Enqueued after torch's
+        current stream; returns what `factorize` returns, when the factorization has finished on the device."""
+        import torch
+        a = A.contents
+        nz = int(_view(a.p, a.ncol + 1, C.c_int64, np.int64)[-1]) if a.p else 0
+        if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float64):
+            raise TypeError("factorize_device: values must be a torch.float64 tensor on the device")
+        if values.dim() != 1 or values.shape[0] != nz or not values.is_contiguous():
+            raise ValueError(f"factorize_device: values must be 1-D, contiguous and of length nnz (A) = {nz}")
+        b = (C.c_double * 2)(beta, 0.0)
+        stream = torch.cuda.current_stream(values.device).cuda_stream
+        return self.L.cholmod_l_hip_factorize_values_device(A, values.data_ptr() or 1, C.byref(b), Lf, stream,
+                                                            C.byref(self.cm))
 
     def refactorize_resident(self, Lf, beta=0.0):
         b = (C.c_double * 2)(beta, 0.0)

@@ -10,8 +10,19 @@
 
 namespace {
 
+/* the product map of the value map goes with it (cholmod_hip_set_product_map) */
+static void drop_product_map (cholmod_hip_plan *P)
+{
+    for (void *d : {(void *) P->d_pm_cp, (void *) P->d_pm_ia, (void *) P->d_pm_ib, (void *) P->d_pm_order}) if (d) (void) hipFree (d) ;
+    P->d_pm_cp = P->d_pm_ia = P->d_pm_ib = nullptr ; P->d_pm_order = nullptr ;
+    P->pm_set = false ; P->pm_na = 0 ;
+}
+
 static void free_device (cholmod_hip_plan *P)
 {
+    drop_product_map (P) ;
+    for (hipEvent_t e : {P->fv_ev_in, P->fv_ev_out}) if (e) (void) hipEventDestroy (e) ;
+    P->fv_ev_in = P->fv_ev_out = nullptr ;
     if (P->prog_dev) { (void) hipHostFree (P->prog_dev) ; P->prog_dev = nullptr ; }
     if (P->h_vals) { (void) hipHostFree (P->h_vals) ; P->h_vals = nullptr ; }
     for (auto e : P->chunk_ev) (void) hipEventDestroy (e) ;
@@ -931,6 +942,7 @@ int cholmod_hip_upload_matrix (cholmod_hip_plan *P, const int64_t *Sp, const int
     P->rs_index_valid = false ;     // ... and the transposed index of the residual goes with the old one
     P->s_cur_nz = nz ;
     P->vsrc_nz = 0 ;                // ... and the value map of the previous one is void
+    drop_product_map (P) ;          // ... with its product map
     P->h_vgather.clear () ; P->nchunks = 0 ;
     if (!Snz && P->world == 1) P->h_Sp.assign (Sp, Sp + n + 1) ; else P->h_Sp.clear () ;
     return CHOLMOD_HIP_OK ;
@@ -940,6 +952,7 @@ int cholmod_hip_set_value_map (cholmod_hip_plan *P, const int64_t *src, int64_t 
 {
     if (!P || P->host_only || !src || !P->d_Sp || P->s_unpacked || snz != P->s_cur_nz || nvalues < 0) return CHOLMOD_HIP_INVALID ;
     for (i64 q = 0 ; q < snz ; q++) if (src [q] < 0 || src [q] >= nvalues) return CHOLMOD_HIP_INVALID ;
+    drop_product_map (P) ;          // (a product map describes the values of ONE value map)
     if (P->d_vsrc) { (void) hipFree (P->d_vsrc) ; P->d_vsrc = nullptr ; }
     if (P->d_vals) { (void) hipFree (P->d_vals) ; P->d_vals = nullptr ; }
     HIPCHK (hipMalloc ((void **) &P->d_vsrc, std::max<i64> (snz, 1) * sizeof (i64))) ;
@@ -1110,6 +1123,98 @@ int cholmod_hip_factorize_resident (cholmod_hip_plan *P, double beta,
     int rc = run_factorize (P, beta, quick_return_if_not_posdef, &m) ;
     if (minor) *minor = m ;
     return rc ;
+}
+
+/* The values of the value map as sums of products of the caller's values (cholmod_hip.h): validated here, entry by
+ * entry, so that k_product_values needs no bounds check of its own; then the lists go up once, with the entries sorted
+ * by list length into the kernel's three classes (a counting sort: inside a class the entries keep their order). */
+int cholmod_hip_set_product_map (cholmod_hip_plan *P, const int64_t *cp, const int64_t *ia, const int64_t *ib,
+    int64_t nc, int64_t navalues)
+{
+    if (!P || P->host_only) return CHOLMOD_HIP_INVALID ;
+    if (!cp) { drop_product_map (P) ; return CHOLMOD_HIP_OK ; }
+    if (!ia || !ib || !P->d_vsrc || P->vsrc_nz != P->s_cur_nz || nc != P->vals_n || nc < 0 || navalues < 0 || cp [0] != 0)
+        return CHOLMOD_HIP_INVALID ;
+    for (i64 c = 0 ; c < nc ; c++) if (cp [c + 1] < cp [c]) return CHOLMOD_HIP_INVALID ;
+    const i64 np = cp [nc] ;
+    if (np > INT32_MAX || nc > INT32_MAX) return CHOLMOD_HIP_TOO_LARGE ;
+    for (i64 p = 0 ; p < np ; p++) if (ia [p] < 0 || ia [p] >= navalues || ib [p] < 0 || ib [p] >= navalues) return CHOLMOD_HIP_INVALID ;
+    drop_product_map (P) ;
+    auto cls = [&] (i64 c) { const i64 len = cp [c + 1] - cp [c] ; return len <= PM_LEN1 ? 0 : len <= PM_LEN16 ? 1 : 2 ; } ;
+    i64 first [4] = {0, 0, 0, 0} ;
+    for (i64 c = 0 ; c < nc ; c++) first [cls (c) + 1]++ ;
+    for (int k = 0 ; k < 3 ; k++) first [k + 1] += first [k] ;
+    std::vector<i32> order ((size_t) nc) ;
+    {
+        i64 next [3] = {first [0], first [1], first [2]} ;
+        for (i64 c = 0 ; c < nc ; c++) order [next [cls (c)]++] = (i32) c ;
+    }
+    const std::vector<i64> vcp (cp, cp + nc + 1), via (ia, ia + np), vib (ib, ib + np) ;
+    hipError_t e = hipSuccess ;
+    P->d_pm_cp = dupload (vcp, e) ;
+    if (e == hipSuccess) P->d_pm_ia = dupload (via, e) ;
+    if (e == hipSuccess) P->d_pm_ib = dupload (vib, e) ;
+    if (e == hipSuccess) P->d_pm_order = dupload (order, e) ;
+    if (e != hipSuccess)
+    {
+        (void) hipGetLastError () ;
+        drop_product_map (P) ;
+        return e == hipErrorOutOfMemory ? CHOLMOD_HIP_OUT_OF_MEMORY : CHOLMOD_HIP_GPU_PROBLEM ;
+    }
+    for (int k = 0 ; k < 4 ; k++) P->pm_class [k] = first [k] ;
+    P->pm_na = navalues ;
+    P->pm_set = true ;
+    return CHOLMOD_HIP_OK ;
+}
+
+/* A values-only factorization whose values are in device memory already (cholmod_hip.h): the engine stream takes its
+ * place behind the caller's, the values go from dvalues straight into the resident S -- through the product kernel and the
+ * plan's d_vals first when they are to be computed -- and the factorization runs as on any resident S: the assembly
+ * (k_assemble_mapped, one value of S per entry of L) is the first to read them.  No pinned buffer, no copy. */
+int cholmod_hip_factorize_values_device (cholmod_hip_plan *P, const double *dvalues, int64_t nvalues,
+    double beta, int quick_return_if_not_posdef, void *stream, int64_t *minor)
+{
+    if (!P || P->host_only || !dvalues || !minor || P->world > 1) return CHOLMOD_HIP_INVALID ;
+    if (P->flags & (CHOLMOD_HIP_CX_STORAGE | CHOLMOD_HIP_PHI_TWIN)) return CHOLMOD_HIP_INVALID ;       // real factors only
+    if (!P->d_Sp || !P->d_vsrc || P->s_unpacked || P->vsrc_nz != P->s_cur_nz) return CHOLMOD_HIP_INVALID ;
+    if (nvalues != (P->pm_set ? P->pm_na : P->vals_n)) return CHOLMOD_HIP_INVALID ;
+    if (P->values_begun) return CHOLMOD_HIP_INVALID ;           // (a host upload is under way: its factorization comes first)
+    hipStream_t user = (hipStream_t) stream, st = P->stream ;
+    if (!P->fv_ev_in) HIPCHK (hipEventCreateWithFlags (&P->fv_ev_in, hipEventDisableTiming)) ;
+    if (!P->fv_ev_out) HIPCHK (hipEventCreateWithFlags (&P->fv_ev_out, hipEventDisableTiming)) ;
+    HIPCHK (hipEventRecord (P->fv_ev_in, user)) ;
+    HIPCHK (hipStreamWaitEvent (st, P->fv_ev_in, 0)) ;
+    const double *vals = dvalues ;
+    if (P->pm_set)
+    {
+        const i64 *c = P->pm_class ;
+#define PM_LAUNCH(G_, K_) if (c [K_ + 1] > c [K_]) \
+            hipLaunchKernelGGL (k_product_values<G_>, dim3 ((unsigned) (((c [K_ + 1] - c [K_]) * G_ + 255) / 256)), dim3 (256), 0, st, \
+                c [K_ + 1] - c [K_], P->d_pm_order + c [K_], P->d_pm_cp, P->d_pm_ia, P->d_pm_ib, dvalues, P->d_vals)
+        PM_LAUNCH (1, 0) ; PM_LAUNCH (16, 1) ; PM_LAUNCH (64, 2) ;
+#undef PM_LAUNCH
+        vals = P->d_vals ;
+    }
+    if (P->vsrc_nz > 0)
+        hipLaunchKernelGGL (k_gather_values, dim3 ((unsigned) ((P->vsrc_nz + 255) / 256)), dim3 (256), 0, st,
+            P->vsrc_nz, P->d_vsrc, vals, P->d_Sx) ;
+    HIPCHK (hipGetLastError ()) ;
+    i64 m = P->n ;
+    const int rc = run_factorize (P, beta, quick_return_if_not_posdef, &m) ;
+    *minor = m ;
+    if (rc < 0) return rc ;
+    // (run_factorize has waited for the engine stream: what the caller enqueues next finds the factor, and dvalues is free)
+    HIPCHK (hipEventRecord (P->fv_ev_out, st)) ;
+    HIPCHK (hipStreamWaitEvent (user, P->fv_ev_out, 0)) ;
+    return rc ;
+}
+
+int cholmod_hip_download_matrix_values (cholmod_hip_plan *P, double *Sx_host)
+{
+    if (!P || P->host_only || !Sx_host || !P->d_Sp || !P->d_Sx) return CHOLMOD_HIP_INVALID ;
+    HIPCHK (hipStreamSynchronize (P->stream)) ;
+    if (P->s_cur_nz > 0) HIPCHK (hipMemcpy (Sx_host, P->d_Sx, (size_t) P->s_cur_nz * sizeof (double), hipMemcpyDeviceToHost)) ;
+    return CHOLMOD_HIP_OK ;
 }
 
 int cholmod_hip_download_factor (cholmod_hip_plan *P, double *Lx_host)

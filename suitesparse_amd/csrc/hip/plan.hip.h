@@ -345,6 +345,14 @@ struct cholmod_hip_plan {
     int *d_first_fail = nullptr ;           // k_first_fail result
     i64 *d_vsrc = nullptr ; double *d_vals = nullptr ;      // value map of the resident S (cholmod_hip_set_value_map)
     i64 vsrc_nz = 0, vals_n = 0, s_cur_nz = 0 ;
+    // values from device memory (cholmod_hip_factorize_values_device): the event the engine stream waits for on the
+    // caller's stream and the one the caller's stream waits for; and the product map (cholmod_hip_set_product_map): the
+    // vals_n values of the value map are sums of products of the pm_na values the caller passes -- lists (pm_cp, pm_ia,
+    // pm_ib), the entries sorted by list length into the three classes of k_product_values (pm_order, pm_class [0 .. 3])
+    hipEvent_t fv_ev_in = nullptr, fv_ev_out = nullptr ;
+    i64 *d_pm_cp = nullptr, *d_pm_ia = nullptr, *d_pm_ib = nullptr ; i32 *d_pm_order = nullptr ;
+    i64 pm_class [4] = {0, 0, 0, 0}, pm_na = 0 ;
+    bool pm_set = false ;
     double *h_vals = nullptr ; i64 h_vals_n = 0 ;           // pinned staging of the value upload (cholmod_hip_values_begin)
     // the upload is staged / pushed chunk by chunk; in batch order the entries of S are sorted by the batch of their column's
     // front (cholmod_hip_set_value_map) and a batch waits for its own chunks only, in S order the assembly waits for all

@@ -808,6 +808,87 @@ cholmod_sparse *ssamd_aat (cholmod_sparse *A, cholmod_sparse *F, int values, int
     return ok ? C : NULL ;
 }
 
+/* The values of C = tril (A*A') as sums of products of the values of A, entry by entry (cholmod.h): list c holds, for
+ * entry c = C (i,j) in the order ssamd_aat (A, NULL, ., lower) stores C, the pairs (position of A (i,k), position of A (j,k))
+ * over the columns k rows i and j share, k ascending -- the terms and the order of ssamd_aat's accumulator.  Integer work
+ * only: the pattern of C, a row index of A that remembers positions, one pass that counts and one that fills. */
+int64_t cholmod_l_hip_aat_product_map (cholmod_sparse *A, int64_t *cp, int64_t *ia, int64_t *ib, cholmod_common *Common)
+{
+    RETURN_IF_NULL_COMMON (-1) ;
+    RETURN_IF_NULL (A, -1) ;
+    if (A->stype != 0 || !A->p || (!A->packed && !A->nz)) { ERROR (CHOLMOD_INVALID, "A must be an unsymmetric matrix (stype 0)") ; return -1 ; }
+    const Int m = (Int) A->nrow, ncol = (Int) A->ncol ;
+    const Int *Ap = A->p, *Ai = A->i, *Anz = A->nz ;
+    Int anz = 0 ;
+    for (Int k = 0 ; k < ncol ; k++)
+    {
+        const Int len = A->packed ? Ap [k+1] - Ap [k] : Anz [k] ;
+        if (len < 0 || Ap [k] < 0 || Ap [k] + len > (Int) A->nzmax) { ERROR (CHOLMOD_INVALID, "invalid column pointers") ; return -1 ; }
+        anz += len ;
+    }
+    if (anz > 0 && !Ai) { ERROR (CHOLMOD_INVALID, "argument missing") ; return -1 ; }
+    for (Int k = 0 ; k < ncol ; k++)
+        for (Int q = Ap [k], qend = q + (A->packed ? Ap [k+1] - Ap [k] : Anz [k]) ; q < qend ; q++)
+            if (Ai [q] < 0 || Ai [q] >= m) { ERROR (CHOLMOD_INVALID, "row index out of range") ; return -1 ; }
+    Common->status = CHOLMOD_OK ;
+    const int fill = (cp || ia || ib) ;
+    cholmod_sparse *Cm = fill ? ssamd_aat (A, NULL, 0, TRUE, Common) : NULL ;
+    if (fill && !Cm) return -1 ;
+    const Int nc = Cm ? ((Int *) Cm->p) [m] : 0 ;
+    /* rows of A: column and position of every entry, columns ascending */
+    Int *Rp = cholmod_l_calloc (m + 2, sizeof (Int), Common) ;
+    Int *Rk = cholmod_l_malloc (anz > 0 ? anz : 1, sizeof (Int), Common) ;
+    Int *Rq = cholmod_l_malloc (anz > 0 ? anz : 1, sizeof (Int), Common) ;
+    Int *slot = fill ? cholmod_l_malloc (m > 0 ? m : 1, sizeof (Int), Common) : NULL ;
+    Int *ptr = fill ? cholmod_l_calloc (nc + 2, sizeof (Int), Common) : NULL ;
+    int64_t npairs = -1 ;
+    if (Rp && Rk && Rq && (!fill || (slot && ptr)))
+    {
+#define COL_END(k) (Ap [k] + (A->packed ? Ap [(k)+1] - Ap [k] : Anz [k]))
+        for (Int k = 0 ; k < ncol ; k++) for (Int q = Ap [k] ; q < COL_END (k) ; q++) Rp [Ai [q] + 2]++ ;
+        for (Int i = 0 ; i < m ; i++) Rp [i + 2] += Rp [i + 1] ;
+        for (Int k = 0 ; k < ncol ; k++)
+            for (Int q = Ap [k] ; q < COL_END (k) ; q++) { const Int r = Rp [Ai [q] + 1]++ ; Rk [r] = k ; Rq [r] = q ; }
+        /* (Rp [j] .. Rp [j+1] is row j now) */
+        const Int *Cp = Cm ? Cm->p : NULL, *Ci = Cm ? Cm->i : NULL ;
+        npairs = 0 ;
+        for (int pass = 0 ; pass < (fill ? 2 : 1) ; pass++)
+        {
+            for (Int j = 0 ; j < m ; j++)
+            {
+                if (fill) for (Int a = Cp [j] ; a < Cp [j+1] ; a++) slot [Ci [a]] = a ;
+                for (Int p = Rp [j] ; p < Rp [j+1] ; p++)
+                {
+                    const Int k = Rk [p] ;
+                    for (Int q = Ap [k] ; q < COL_END (k) ; q++)
+                    {
+                        const Int i = Ai [q] ;
+                        if (i < j) continue ;
+                        if (!fill) { npairs++ ; continue ; }
+                        if (pass == 0) { ptr [slot [i] + 1]++ ; npairs++ ; continue ; }
+                        const Int d = ptr [slot [i]]++ ;
+                        if (ia) ia [d] = q ;
+                        if (ib) ib [d] = Rq [p] ;
+                    }
+                }
+            }
+            if (fill && pass == 0)
+            {
+                for (Int c = 0 ; c < nc ; c++) ptr [c + 1] += ptr [c] ;
+                if (cp) for (Int c = 0 ; c <= nc ; c++) cp [c] = ptr [c] ;
+            }
+        }
+#undef COL_END
+    }
+    if (Rp) cholmod_l_free (m + 2, sizeof (Int), Rp, Common) ;
+    if (Rk) cholmod_l_free (anz > 0 ? anz : 1, sizeof (Int), Rk, Common) ;
+    if (Rq) cholmod_l_free (anz > 0 ? anz : 1, sizeof (Int), Rq, Common) ;
+    if (slot) cholmod_l_free (m > 0 ? m : 1, sizeof (Int), slot, Common) ;
+    if (ptr) cholmod_l_free (nc + 2, sizeof (Int), ptr, Common) ;
+    if (Cm) cholmod_l_free_sparse (&Cm, Common) ;
+    return npairs ;
+}
+
 cholmod_sparse *cholmod_l_transpose (cholmod_sparse *A, int values, cholmod_common *Common)
 {
     return cholmod_l_ptranspose (A, values, NULL, NULL, 0, Common) ;

@@ -716,6 +716,7 @@ int cholmod_l_factorize_p (cholmod_sparse *A, double beta [2], SuiteSparse_long 
     }
     if (!S) return FALSE ;
     L->hip_apat_valid = FALSE ;
+    L->hip_aat_valid = FALSE ;              /* (the engine drops a product map with the value map it belongs to) */
     if (ltiming) tl1 = api_now () ;
     int ok = cholmod_l_super_numeric (S, NULL, beta ? beta : zero, L, Common) ;
     if (ltiming) tl2 = api_now () ;
@@ -750,6 +751,81 @@ int cholmod_l_factorize_p (cholmod_sparse *A, double beta [2], SuiteSparse_long 
             tl1 - tl0, tl2 - tl1, tl3 - tl2) ;
     }
     return ok ;
+}
+
+/* cholmod_l_factorize for values of A that live in device memory (cholmod.h).  The proof that the resident matrix and its
+ * value map fit A is the pattern hash, taken BEFORE anything is enqueued here (the host path overlaps it with the upload;
+ * there is no upload to hide it behind): a mismatch touches no device state. */
+int cholmod_l_hip_factorize_values_device (cholmod_sparse *A, const double *Ax_dev, double beta [2],
+    cholmod_factor *L, void *stream, cholmod_common *Common)
+{
+    RETURN_IF_NULL_COMMON (FALSE) ;
+    RETURN_IF_NULL (A, FALSE) ;
+    RETURN_IF_NULL (Ax_dev, FALSE) ;
+    RETURN_IF_NULL (L, FALSE) ;
+    RETURN_IF_NULL (A->p, FALSE) ;
+    if (A->xtype == CHOLMOD_COMPLEX || A->xtype == CHOLMOD_ZOMPLEX || L->xtype == CHOLMOD_COMPLEX || L->xtype == CHOLMOD_ZOMPLEX)
+    { ERROR (CHOLMOD_NOT_INSTALLED, "a factorization from device values of a complex matrix or factor is not supported") ; return FALSE ; }
+    if (A->xtype != CHOLMOD_REAL && A->xtype != CHOLMOD_PATTERN) { ERROR (CHOLMOD_INVALID, "invalid xtype") ; return FALSE ; }
+    if (!A->packed) { ERROR (CHOLMOD_INVALID, "A must be packed") ; return FALSE ; }
+    if (A->nrow != L->n || (A->stype != 0 && A->nrow != A->ncol)) { ERROR (CHOLMOD_INVALID, "A and L dimensions do not match") ; return FALSE ; }
+    if (L->xtype != CHOLMOD_REAL || !L->is_super)
+    { ERROR (CHOLMOD_INVALID, "L must be a numeric supernodal factor (factorize from the host first)") ; return FALSE ; }
+    /* device pointers cannot be read on the host: no fallback, whatever Common->hip_cpu_fallback says */
+    if (ssamd_resolve_use_gpu (Common) != 1) { ERROR (CHOLMOD_INVALID, "a factorization from device values needs Common->useGPU") ; return FALSE ; }
+    if (Common->hip_world > 1) { ERROR (CHOLMOD_INVALID, "the factorization from device values runs on one rank only") ; return FALSE ; }
+    if (!L->hip_plan || !L->hip_apat_valid)
+    { ERROR (CHOLMOD_INVALID, "L holds no pattern record: cholmod_l_factorize from a host matrix of this pattern first") ; return FALSE ; }
+    const size_t annz = (size_t) ((Int *) A->p) [A->ncol] ;
+    if (annz > 0 && !A->i) { ERROR (CHOLMOD_INVALID, "argument missing") ; return FALSE ; }
+    Common->status = CHOLMOD_OK ;
+    cholmod_hip_plan *plan = (cholmod_hip_plan *) L->hip_plan ;
+    uint64_t hash [2] ;
+    hash [0] = pattern_hash (A, &hash [1]) ;
+    if (A->stype != 0)
+    {
+        if (L->hip_apat_nnz != annz || L->hip_apat_hash != hash [0] || L->hip_apat_hash2 != hash [1])
+        { ERROR (CHOLMOD_INVALID, "A does not have the pattern L was last factorized from") ; return FALSE ; }
+    }
+    else if (!(L->hip_aat_valid && L->hip_aat_nnz == annz && L->hip_aat_hash == hash [0] && L->hip_aat_hash2 == hash [1]))
+    {
+        /* the resident matrix is tril (A*A'): its pattern from A's, against the record; then the lists of products */
+        cholmod_sparse *Cm = ssamd_aat (A, NULL, 0, TRUE, Common) ;
+        if (!Cm) return FALSE ;
+        uint64_t chash [2] ;
+        chash [0] = pattern_hash (Cm, &chash [1]) ;
+        const size_t cnz = (size_t) ((Int *) Cm->p) [Cm->ncol] ;
+        cholmod_l_free_sparse (&Cm, Common) ;
+        if (L->hip_apat_nnz != cnz || L->hip_apat_hash != chash [0] || L->hip_apat_hash2 != chash [1])
+        { ERROR (CHOLMOD_INVALID, "A*A' does not have the pattern L was last factorized from") ; return FALSE ; }
+        const int64_t npairs = cholmod_l_hip_aat_product_map (A, NULL, NULL, NULL, Common) ;
+        if (npairs < 0) return FALSE ;
+        if (npairs > INT32_MAX) { ERROR (CHOLMOD_TOO_LARGE, "too many products for the product map") ; return FALSE ; }
+        const size_t np1 = npairs > 0 ? (size_t) npairs : 1 ;
+        int64_t *cp = cholmod_l_malloc (cnz + 1, sizeof (int64_t), Common) ;
+        int64_t *ia = cholmod_l_malloc (np1, sizeof (int64_t), Common) ;
+        int64_t *ib = cholmod_l_malloc (np1, sizeof (int64_t), Common) ;
+        int rm = CHOLMOD_HIP_OUT_OF_MEMORY ;
+        if (cp && ia && ib && cholmod_l_hip_aat_product_map (A, cp, ia, ib, Common) == npairs)
+            rm = cholmod_hip_set_product_map (plan, cp, ia, ib, (int64_t) cnz, (int64_t) annz) ;
+        if (cp) cholmod_l_free (cnz + 1, sizeof (int64_t), cp, Common) ;
+        if (ia) cholmod_l_free (np1, sizeof (int64_t), ia, Common) ;
+        if (ib) cholmod_l_free (np1, sizeof (int64_t), ib, Common) ;
+        L->hip_aat_valid = FALSE ;
+        if (rm != CHOLMOD_HIP_OK)
+        {
+            if (Common->status < CHOLMOD_OK) return FALSE ;       /* (out of host memory: reported already) */
+            return map_hip_status (rm, Common, "the product map could not be stored on the device") ;
+        }
+        L->hip_aat_hash = hash [0] ; L->hip_aat_hash2 = hash [1] ; L->hip_aat_nnz = annz ;
+        L->hip_aat_valid = TRUE ;
+    }
+    int64_t minor = (int64_t) L->n ;
+    const int rc = cholmod_hip_factorize_values_device (plan, Ax_dev, (int64_t) annz, beta ? beta [0] : 0.0,
+        Common->quick_return_if_not_posdef, stream, &minor) ;
+    /* (the engine refuses before it touches the device: L keeps its factor) */
+    if (rc == CHOLMOD_HIP_INVALID) { ERROR (CHOLMOD_INVALID, "the plan holds no value map for this matrix") ; return FALSE ; }
+    return finish_numeric (rc, minor, L, Common) ;
 }
 
 int cholmod_l_factorize (cholmod_sparse *A, cholmod_factor *L, cholmod_common *Common)
@@ -862,7 +938,7 @@ int cholmod_l_change_factor (int to_xtype, int to_ll, int to_super, int to_packe
         if (L->cx_twin) cholmod_l_free_factor ((cholmod_factor **) &L->cx_twin, Common) ;
         L->xtype = CHOLMOD_PATTERN ; L->dtype = CHOLMOD_DOUBLE ;
         L->minor = L->n ; L->is_ll = TRUE ;
-        L->hip_on_device = FALSE ; L->hip_host_valid = FALSE ; L->hip_apat_valid = FALSE ;
+        L->hip_on_device = FALSE ; L->hip_host_valid = FALSE ; L->hip_apat_valid = FALSE ; L->hip_aat_valid = FALSE ;
         return TRUE ;
     }
     if (L->xtype != CHOLMOD_PATTERN) return TRUE ;       /* already numeric (:1129-1136: nothing to do) */
