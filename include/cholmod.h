@@ -416,6 +416,27 @@ int cholmod_l_hip_residual_device (cholmod_factor *L, const double *X_dev, size_
     double *R_dev, size_t ldr, size_t nrhs, double *Rnorm_dev, void *stream, cholmod_common *Common) ;
 int cholmod_l_hip_refine_device (cholmod_factor *L, const double *B_dev, size_t ldb, double *X_dev, size_t ldx,
     size_t nrhs, int steps, double *Rnorm_dev, void *stream, cholmod_common *Common) ;
+/* The selected inverse (the sparse inverse subset; the reference ships it as MATLAB_Tools/sparseinv): the entries of
+ * Z = (A + beta I)^-1 on the pattern of L -- hence on the pattern of A -- for the A and beta L was last factorized from ON
+ * THE DEVICE, computed there from the resident factor (cholmod_hip_selinv_device: supernodal Takahashi on fp64 MFMA).
+ * Marginal variances of a Gaussian Markov random field, the gradient of log det A, trace estimators.
+ * cholmod_l_hip_selinv_device: Z_dev (NULL, or a device pointer to nnz (A) doubles) receives Z at every entry of A, in A's
+ * entry order -- a quiet NaN where the factorization does not read A (the ignored triangle of a symmetric A, entries
+ * outside L's pattern); diag_dev (NULL, or n doubles on the device) receives diag (Z) in A's ordering.  A gives the
+ * PATTERN only and is hashed against the record of the values-only path (L->hip_apat_valid) exactly as
+ * cholmod_l_hip_factorize_values_device does: a mismatch touches no device state; A == NULL is legal when Z_dev is.
+ * The inverse is computed if the resident one is stale (any factorization makes it so), then gathered; the call takes its
+ * place on `stream` as cholmod_l_hip_solve_device does and the host does not wait once the workspaces exist.
+ * FALSE with CHOLMOD_INVALID for a NULL L, both outputs NULL, a symbolic L, L->minor < n, the GPU switched off (no host
+ * fallback: Common->hip_cpu_fallback does not apply), several ranks, an L not factorized on the device; with Z_dev also
+ * for a NULL, unsymmetric (stype == 0: A*A' and column subsets are not served) or unpacked A, mismatched dimensions, an L
+ * without the pattern record; with CHOLMOD_NOT_INSTALLED for a complex or zomplex A or L -- all before a device is touched. */
+int cholmod_l_hip_selinv_device (cholmod_sparse *A, cholmod_factor *L, double *Z_dev, double *diag_dev, void *stream,
+    cholmod_common *Common) ;
+/* The whole subset on the host: Zx receives L->xsize doubles indexed by L->super / pi / px / s exactly like L->x
+ * (Z (s [pi [k] + i], super [k] + j), i >= j, at px [k] + i + j nsrow; zeros above the diagonal of the diagonal blocks), in
+ * the factor's ordering.  Computes the inverse if it is stale and waits for it.  Refusals as above. */
+int cholmod_l_hip_selinv_to_host (cholmod_factor *L, double *Zx, cholmod_common *Common) ;
 /* cholmod_l_factorize for new VALUES of A that already live in device memory (a matrix assembled on the GPU: the step of a
  * Newton, time-stepping or interior-point loop), without a trip through the host.  A supplies the PATTERN only (p, i,
  * stype, packed; A->x is never read and may be NULL); Ax_dev is a device pointer to nnz (A) doubles in A's own entry

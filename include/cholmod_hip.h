@@ -362,6 +362,47 @@ int cholmod_hip_residual_device (cholmod_hip_plan *plan, int perm, const double 
 int cholmod_hip_refine_device (cholmod_hip_plan *plan, int perm, const double *dB, int64_t ldb, double *dX, int64_t ldx,
     int64_t nrhs, int steps, double *dRnorm, void *stream) ;
 
+/* (This entry point and the four after it: csrc/hip/selinv.hip.)
+ * The selected inverse: Zx = the entries of Z = (L L')^-1 = (P (A + beta I) P')^-1 on the pattern of L, a second array of
+ * xsize doubles in HBM in exactly the layout of Lx -- supernode s holds, column-major nsrow x nscol at px [s], the values
+ * Z (s [pi [s] + i], super [s] + j) for i >= j; the dead strictly-upper triangle of every diagonal block is exact zero.
+ * The reference computes the same subset column by column on a simplicial LDL' (MATLAB_Tools/sparseinv/sparseinv.c,
+ * Takahashi's equations); here it is the multifrontal factorization run backwards: the plan's batches from the last to
+ * the first, per front 64-column blocks from the last to the first, Z [R, b] = -Z [R, R] L [R, b] inv (L_bb) on
+ * v_mfma_f64_16x16x4 (R = the front's rows behind the block), Z [b, b] from two triangular solves; a front's Z on its
+ * below-rows is gathered from the finished panels of its ancestors.  Every entry has one owner and a fixed summation
+ * order: two calls on the same factor give the same bits.
+ * Ordered on `stream` exactly as cholmod_hip_solve_device is: the engine stream waits for an event recorded on it, `stream`
+ * waits for the engine's completion event; the first call builds the launch program and allocates Zx and the scratch
+ * (the squares of the fronts in flight, CHOLMOD_HIP_SELINV_BUDGET_MB of them at most at a time, 2048 by default, and the
+ * partial sums of the diagonal blocks), after that nothing is allocated and the host does not wait.  Not during capture.
+ * Zx stays resident until cholmod_hip_selinv_release or cholmod_hip_plan_destroy; any factorization,
+ * cholmod_hip_upload_factor or cholmod_hip_upload_matrix marks it stale.
+ * All five return CHOLMOD_HIP_INVALID, before any device call, for a NULL plan, a host-only plan, several ranks, no numeric
+ * factor on the device, a last factorization that was not positive definite, and the plans of complex factors
+ * (CHOLMOD_HIP_PHI_TWIN, CHOLMOD_HIP_CX_STORAGE); CHOLMOD_HIP_OUT_OF_MEMORY when Zx and the scratch do not fit: what the
+ * call allocated is freed, the factor is untouched. */
+int cholmod_hip_selinv_device (cholmod_hip_plan *plan, void *stream) ;
+/* What a caller takes from a current Zx, on the device and ordered on `stream` as above; either pointer may be NULL.
+ * dZvalues [k], k < nvalues in the order of the value map (the array cholmod_hip_factorize_values_device takes), receives Z
+ * at the position of the caller's entry k; a value the resident S does not read -- the ignored triangle, all but the last
+ * of equal neighbours, entries outside the pattern of L -- receives a quiet NaN (the convention of cholmod_l_solve2's
+ * subsets).  dDiag [i] receives (A + beta I)^-1 (i, i): in the caller's ordering with perm = 1 (cholmod_hip_set_perm
+ * first), in the factor's with perm = 0.  A pure gather, bit-identical to the entries of Zx; the position of an entry
+ * comes from the supernode map and a search in the supernode's row list.  CHOLMOD_HIP_INVALID also: no current Zx;
+ * dZvalues without a value map of the current resident packed S, with another nvalues than the map's, or with a product
+ * map set (the caller's values are then not the entries of S); perm without a permutation. */
+int cholmod_hip_selinv_gather_device (cholmod_hip_plan *plan, double *dZvalues, int64_t nvalues, double *dDiag, int perm,
+    void *stream) ;
+/* Zx (xsize doubles) to the host; waits for the engine stream.  CHOLMOD_HIP_INVALID without a current Zx. */
+int cholmod_hip_selinv_download (cholmod_hip_plan *plan, double *Zx_host) ;
+/* frees Zx and the scratch (the launch program stays); the next cholmod_hip_selinv_device allocates them again */
+int cholmod_hip_selinv_release (cholmod_hip_plan *plan) ;
+/* out8: [0] device seconds of the last cholmod_hip_selinv_device (two events, read here: may wait for it)  [1] its kernel
+ * launches  [2] flops of the hot product, sum of 2 |R|^2 nb over the blocks  [3] all flops  [4] bytes of Zx  [5] bytes of
+ * scratch  [6] 1 if Zx is current  [7] reserved, zero */
+int cholmod_hip_selinv_info (cholmod_hip_plan *plan, double *out8) ;
+
 /* Parity hooks: copy derived integer maps back to the host.
  *  sparent  [nsuper]     supernodal etree (reference :1025)
  *  level    [nsuper]     height of s in that tree (leaves 0)

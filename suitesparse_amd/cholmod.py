@@ -32,6 +32,8 @@ SYS_A, SYS_LDLt, SYS_LD, SYS_DLt, SYS_L, SYS_Lt, SYS_D, SYS_P, SYS_Pt = range(9)
 HIP_PLAN_HOST_ONLY = 2
 # plan flags (include/cholmod_hip.h)
 HIP_WIDE_OB, HIP_NO_FUSED_POTRF, HIP_NO_FUSED_TRSM, HIP_PHI_TWIN = 128, 512, 1024, 16384
+HIP_NO_SMALL_FRONTS = 16
+HIP_OK = 0
 HIP_INVALID = -4
 HIP_NO_DEVICE = -1
 
@@ -146,6 +148,7 @@ API_SYMBOLS = [
     "cholmod_l_gather_factor", "cholmod_l_hip_prepare", "cholmod_l_hip_front_reach",
     "cholmod_l_hip_solve_device", "cholmod_l_hip_residual_device", "cholmod_l_hip_refine_device",
     "cholmod_l_hip_factorize_values_device", "cholmod_l_hip_aat_product_map",
+    "cholmod_l_hip_selinv_device", "cholmod_l_hip_selinv_to_host",
 ]
 HIP_SYMBOLS = [
     "cholmod_hip_probe", "cholmod_hip_memorysize", "cholmod_hip_set_device", "cholmod_hip_device_count",
@@ -159,8 +162,8 @@ HIP_SYMBOLS = [
     "cholmod_hip_download_factor", "cholmod_hip_download_even_columns", "cholmod_hip_upload_factor", "cholmod_hip_solve",
     "cholmod_hip_set_perm", "cholmod_hip_solve_device", "cholmod_hip_residual_device", "cholmod_hip_refine_device",
     "cholmod_hip_get_maps", "cholmod_hip_get_stats", "cholmod_hip_set_profiling",
-    
-    
+    "cholmod_hip_selinv_device", "cholmod_hip_selinv_gather_device", "cholmod_hip_selinv_download",
+    "cholmod_hip_selinv_release", "cholmod_hip_selinv_info",
     "cholmod_hip_dense_partial_factor", "cholmod_hip_factor_checks", "cholmod_hip_factor_checks_local", "cholmod_hip_get_launch_profile", "cholmod_hip_debug_thin_cycles", "cholmod_hip_debug_launch_regions",
     "cholmod_hip_rccl_unique_id", "cholmod_hip_rccl_attach", "cholmod_hip_rccl_detach",
     "cholmod_hip_version",
@@ -299,6 +302,13 @@ def lib(hooks=None):
     sig("cholmod_hip_download_matrix_values", C.c_int, [vp, vp])
     sig("cholmod_l_hip_factorize_values_device", C.c_int, [sp, vp, C.POINTER(dbl * 2), fc, vp, cm])
     sig("cholmod_l_hip_aat_product_map", i64, [sp, vp, vp, vp, cm])
+    sig("cholmod_hip_selinv_device", C.c_int, [vp, vp])
+    sig("cholmod_hip_selinv_gather_device", C.c_int, [vp, vp, i64, vp, C.c_int, vp])
+    sig("cholmod_hip_selinv_download", C.c_int, [vp, vp])
+    sig("cholmod_hip_selinv_release", C.c_int, [vp])
+    sig("cholmod_hip_selinv_info", C.c_int, [vp, vp])
+    sig("cholmod_l_hip_selinv_device", C.c_int, [sp, fc, vp, vp, vp, cm])
+    sig("cholmod_l_hip_selinv_to_host", C.c_int, [fc, vp, cm])
     sig("cholmod_hip_get_maps", C.c_int, [vp, vp, vp, vp])
     sig("cholmod_hip_get_stats", C.c_int, [vp, vp])
     sig("cholmod_hip_set_profiling", C.c_int, [vp, C.c_int])
@@ -578,6 +588,37 @@ class Session:
         if not ok:
             raise RuntimeError(f"cholmod_l_hip_refine_device failed, status {self.cm.status}")
         return (X, nrm) if norms else X
+
+    def selinv_device(self, A, Lf, values=True, diag=True):
+        """cholmod_l_hip_selinv_device: the selected inverse of the matrix Lf was last factorized from on the device
+        (plus beta I).  Returns (Z, d) as torch.float64 device tensors, None for the part not asked for: Z of length
+        nnz (A), the inverse at the entries of A in A's entry order (NaN where the factorization does not read A), d of
+        length n, its diagonal in A's ordering.  A gives the pattern only (None is allowed with values=False).  Enqueued
+        on torch's current stream; two calls on the same factor give the same bits."""
+        import torch
+        n = int(Lf.contents.n)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        Z = d = None
+        if values:
+            a = A.contents
+            nz = int(_view(a.p, a.ncol + 1, C.c_int64, np.int64)[-1]) if a.p else 0
+            Z = torch.empty(nz, dtype=torch.float64, device=dev)
+        if diag:
+            d = torch.empty(n, dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ok = self.L.cholmod_l_hip_selinv_device(A, Lf, (Z.data_ptr() or 1) if values else None,
+                                                (d.data_ptr() or 2) if diag else None, stream, C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_selinv_device failed, status {self.cm.status}")
+        return Z, d
+
+    def selinv_host(self, Lf):
+        """cholmod_l_hip_selinv_to_host: the selected inverse in the layout of L->x (FactorView.x), xsize doubles, in
+        the factor's ordering; computed on the device if the resident one is stale."""
+        out = np.zeros(max(int(Lf.contents.xsize), 1))
+        if not self.L.cholmod_l_hip_selinv_to_host(Lf, out.ctypes.data, C.byref(self.cm)):
+            raise RuntimeError(f"cholmod_l_hip_selinv_to_host failed, status {self.cm.status}")
+        return out[:int(Lf.contents.xsize)]
 
     def solve_subset(self, Lf, b, bset, sys=SYS_A, handles=None):
         """cholmod_l_solve2 with a sparse right-hand side: b (length n, only its entries at the indices `bset` are

@@ -21,6 +21,7 @@ static void drop_product_map (cholmod_hip_plan *P)
 static void free_device (cholmod_hip_plan *P)
 {
     drop_product_map (P) ;
+    selinv_free (P) ;
     for (hipEvent_t e : {P->fv_ev_in, P->fv_ev_out}) if (e) (void) hipEventDestroy (e) ;
     P->fv_ev_in = P->fv_ev_out = nullptr ;
     if (P->prog_dev) { (void) hipHostFree (P->prog_dev) ; P->prog_dev = nullptr ; }
@@ -417,6 +418,7 @@ static int factorize_prologue (cholmod_hip_plan *P)
 {
     hipStream_t st = P->stream ;
     P->winv_valid = false ;                 // the diagonal-block inverses follow the factor
+    P->si_valid = false ; P->factor_state = 0 ;     // ... and so does the selected inverse
     HIPCHK (hipEventRecord (P->ev0, st)) ;
     // Lx := 0 (several ranks: the rank's own fronts -- its d_Lx holds nothing else); the complete
     // factor a gather may have left in d_Lx_full is stale from here on
@@ -674,6 +676,7 @@ static int run_factorize (cholmod_hip_plan *P, double beta, int quick, i64 *mino
         if (ra != CHOLMOD_HIP_OK) return ra ;
     }
     *minor = P->n ;
+    P->factor_state = sbad < 0 ? 1 : 2 ;
     if (sbad < 0) return CHOLMOD_HIP_OK ;
     const FrontD &f = P->fr [sbad] ;
     *minor = f.k1 + binfo - 1 ;
@@ -940,6 +943,7 @@ int cholmod_hip_upload_matrix (cholmod_hip_plan *P, const int64_t *Sp, const int
     P->s_unpacked = (Snz != nullptr) ;
     P->amap_valid = false ;         // a new pattern may have come with the new values
     P->rs_index_valid = false ;     // ... and the transposed index of the residual goes with the old one
+    P->si_valid = false ;           // ... and the selected inverse is that of the old matrix
     P->s_cur_nz = nz ;
     P->vsrc_nz = 0 ;                // ... and the value map of the previous one is void
     drop_product_map (P) ;          // ... with its product map
@@ -1245,6 +1249,7 @@ int cholmod_hip_upload_factor (cholmod_hip_plan *P, const double *Lx_host)
     }
     HIPCHK (hipMemcpy (Lw, Lx_host, P->xsize * sizeof (double), hipMemcpyHostToDevice)) ;
     P->winv_valid = false ;
+    P->si_valid = false ; P->factor_state = 1 ;
     P->full_valid = P->world > 1 ;
     return CHOLMOD_HIP_OK ;
 }

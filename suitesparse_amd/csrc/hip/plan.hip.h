@@ -2,7 +2,8 @@
 // contribution-block arena allocator, the RCCL entry points bound at run time, and the plan itself (cholmod_hip_plan:
 // one symbolic factor prepared for one rank).  plan_build.hip derives the plan (etree, ownership, layout, batches),
 // schedule_dense.hip the launches of a batch of fronts, engine.hip uploads and runs it, exchange.hip moves what its ranks
-// share, solve.hip solves with its factor, residual.hip forms residuals with its resident matrix.
+// share, solve.hip solves with its factor, residual.hip forms residuals with its resident matrix, selinv.hip inverts on
+// the factor's pattern.
 #pragma once
 #include "descriptors.hip.h"
 #include "../../../include/cholmod_hip.h"
@@ -384,6 +385,11 @@ struct cholmod_hip_plan {
     i64 *d_rs_Tp = nullptr, *d_rs_Tq = nullptr ; i32 *d_rs_Tj = nullptr ; bool rs_index_valid = false ;
     double *d_rs_X = nullptr, *d_rs_B = nullptr ;
     hipEvent_t rs_ev_out = nullptr ;
+    // selected inverse (selinv.hip): its program, buffers and events live behind `si`.  factor_state follows the numeric
+    // factor in d_Lx (0: none, 1: positive definite, 2: the last factorization was not); si_valid: Zx belongs to that factor
+    struct SelInv *si = nullptr ;
+    bool si_valid = false ;
+    int factor_state = 0 ;
     // progress of the running factorization, readable from another host thread (cholmod_hip_progress): the host side
     // counts what it has enqueued; with markers enabled the device writes, in stream order, the sequence number of the
     // exchange it has entered / left into pinned host memory (prog_dev [0] / [1])
@@ -402,6 +408,9 @@ struct cholmod_hip_plan {
 // rank's own array when there is one rank, the gathered copy otherwise (nullptr before a gather).
 static inline double *whole_factor (cholmod_hip_plan *P) { return P->world == 1 ? P->d_Lx : (P->full_valid ? P->d_Lx_full : nullptr) ; }
 static inline const FrontD *whole_fronts (cholmod_hip_plan *P) { return P->world == 1 ? P->d_fr : P->d_fr_full ; }
+
+// selinv.hip: everything the selected inverse holds of a plan (cholmod_hip_plan_destroy)
+void selinv_free (cholmod_hip_plan *P) ;
 
 namespace sship {
 

@@ -1,0 +1,357 @@
+// selinv_kernels.hip.h -- device code of the selected inverse (selinv.hip): Z = (L L')^-1 on the pattern of L, front by
+// front from the roots down.  For a column block b = [b0, b1) of a front (at most SI_NB wide) and R = the front's rows
+// after b1 (its later columns, then its below-rows), with M = Z [R, R] known:
+//     T        = M L [R, b]                                   (the hot product: v_mfma_f64_16x16x4, K = |R|)
+//     Z [R, b] = -T inv (L [b, b])                            (a row-wise solve against L_bb: no explicit inverse)
+//     Z [b, b] = inv (L_bb)' (I + L [R, b]' T) inv (L_bb)     (two triangular solves)
+// which is Takahashi's  Z_Rb = -Z_RR G,  Z_bb = inv (L_bb)' inv (L_bb) - G' Z_Rb  with G = L_Rb inv (L_bb), written so that
+// G never exists in memory.  A generic front lives in flight as a full symmetric square (ld = nsrow, both triangles
+// filled) in the scratch buffer; a thin front (one block, nsrow <= SM_MAX) is done whole by one workgroup in LDS.
+// Every entry of Zx has one owner and one summation order: no atomics, the same factor gives the same bits.
+#pragma once
+#include "descriptors.hip.h"
+
+namespace sship {
+
+#define SI_NB 64            /* column block of the recurrence */
+#define SI_KC 64            /* k-chunk of L [R, b] staged in LDS by k_si_block */
+#define SI_BLD 68           /* ... its leading dimension (k-major, column fastest) */
+#define SI_TLD 65           /* leading dimension of the 64 x 64 LDS tiles that lanes walk by column */
+#define SI_PTILE (SI_NB * SI_NB)    /* doubles of one partial of L [R, b]' T (one per 64-row slice of R) */
+#define SI_BLOCK_LDS ((SI_NB * SI_TLD + SI_KC * SI_BLD) * sizeof (double))    /* k_si_block, k_si_diag: two tiles */
+#define SI_THIN_LDS_MAX (160 * 1024)  /* k_si_thin: a front of SM_MAX rows needs at most 18 366 doubles */
+
+// a generic front in flight: its square in the scratch buffer
+struct SiSlot { i32 front ; i32 pad ; i64 moff ; } ;
+// one unit of a launch; the workgroups [wg0, wg0 of the next task) belong to it.  k_si_fill: one workgroup per column of
+// Z [I, I]; k_si_block: one per 64-row slice of R (nslices of them, partials at poff); k_si_diag: one; k_si_store: one per
+// panel column
+struct SiTask { i32 slot ; i32 b0 ; i32 nb ; i32 wg0 ; i32 nslices ; i32 pad ; i64 poff ; } ;
+
+typedef double si_d4 __attribute__ ((ext_vector_type (4))) ;
+
+// the task workgroup `bid` belongs to (tasks sorted by wg0, tasks [0].wg0 == 0)
+__device__ __forceinline__ int si_find (const SiTask *t, int nt, int bid)
+{
+    int lo = 0, hi = nt - 1 ;
+    while (lo < hi)
+    {
+        const int mid = (lo + hi + 1) >> 1 ;
+        if (t [mid].wg0 <= bid) lo = mid ; else hi = mid - 1 ;
+    }
+    return lo ;
+}
+
+// Where Z (r, c), r >= c (the factor's ordering), lives in Zx: column c belongs to supernode supermap [c], row r is found
+// in that supernode's row list -- its own columns first, a binary search below them.  -1: not in the pattern of L.
+__device__ __forceinline__ i64 si_locate (const FrontD &t, const i64 *Ls, i64 r, i64 c)
+{
+    const i64 base = t.psx + (c - t.k1) * (i64) t.nsrow ;
+    if (r < (i64) t.k1 + t.nscol) return base + (r - t.k1) ;
+    const i64 *rows = Ls + t.psi ;
+    int lo = t.nscol, hi = t.nsrow ;
+    while (lo < hi) { const int mid = (lo + hi) >> 1 ; if (rows [mid] < r) lo = mid + 1 ; else hi = mid ; }
+    return (lo < t.nsrow && rows [lo] == r) ? base + lo : -1 ;
+}
+
+__device__ __forceinline__ double si_nan () { return __longlong_as_double (0x7ff8000000000000LL) ; }
+
+// M [I, I] of every front of the launch, both triangles, from the finished panels of its ancestors: a gather by the
+// reader (one workgroup per column of I), never a scatter by several writers.
+__global__ void __launch_bounds__(256) k_si_fill (const SiTask *tasks, int nt, const SiSlot *slots, const FrontD *fr,
+    const i32 *supermap, const i64 *Ls, const double *Zx, double *M)
+{
+    const SiTask T = tasks [si_find (tasks, nt, blockIdx.x)] ;
+    const SiSlot S = slots [T.slot] ;
+    const FrontD &f = fr [S.front] ;
+    const int j = blockIdx.x - T.wg0, ld = f.nsrow, nscol = f.nscol, ncb = f.nsrow - f.nscol ;
+    if (j >= ncb) return ;
+    const i64 *I = Ls + f.psi + nscol ;
+    const i64 c = I [j] ;
+    const FrontD &t = fr [supermap [c]] ;
+    double *Mf = M + S.moff ;
+    for (int i = j + threadIdx.x ; i < ncb ; i += 256)
+    {
+        const i64 q = si_locate (t, Ls, I [i], c) ;
+        const double v = q >= 0 ? Zx [q] : si_nan () ;
+        Mf [(i64) (nscol + i) + (i64) (nscol + j) * ld] = v ;
+        Mf [(i64) (nscol + j) + (i64) (nscol + i) * ld] = v ;
+    }
+}
+
+// X L_bb = B by rows, in place: row i of the nb columns of X (X [i + c ldx]); Lb = entry (0, 0) of L_bb, ld = ldl
+__device__ __forceinline__ void si_row_solve (double *X, int ldx, int i, const double *Lb, i64 ldl, int nb)
+{
+    for (int c = nb - 1 ; c >= 0 ; c--)
+    {
+        const double *Lc = Lb + (i64) c * ldl ;
+        double s = X [i + c * ldx] ;
+        for (int k = c + 1 ; k < nb ; k++) s -= X [i + k * ldx] * Lc [k] ;
+        X [i + c * ldx] = s / Lc [c] ;
+    }
+}
+
+// L_bb' X = B by columns, in place: column c of X
+__device__ __forceinline__ void si_col_solve (double *X, int ldx, int c, const double *Lb, i64 ldl, int nb)
+{
+    for (int a = nb - 1 ; a >= 0 ; a--)
+    {
+        const double *La = Lb + (i64) a * ldl ;
+        double s = X [a + c * ldx] ;
+        for (int k = a + 1 ; k < nb ; k++) s -= La [k] * X [k + c * ldx] ;
+        X [a + c * ldx] = s / La [a] ;
+    }
+}
+
+// One 64-row slice of R of one block: T = M [slice, R] L [R, b] on the matrix cores (M read once, straight from the
+// scratch; L [R, b] through LDS in k-chunks), the slice's partial of L [R, b]' T, then Z [slice, b] = -T inv (L_bb) into the
+// square, mirrored.  Rows past |R| are clamped on the way in and masked on the way out; k past |R| and columns past nb
+// contribute zeros.
+__global__ void __launch_bounds__(256) k_si_block (const SiTask *tasks, int nt, const SiSlot *slots, const FrontD *fr,
+    const double *Lx, double *M, double *Pbuf)
+{
+    extern __shared__ __attribute__ ((aligned (16))) double si_lds [] ;
+    double *Ts = si_lds ;                           // T, then W: [i + SI_TLD c]
+    double *Bs = si_lds + SI_NB * SI_TLD ;          // chunk of L [R, b]: [k SI_BLD + c]; then L [slice, b]: [i + 64 a]; then L_bb
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lk = lane >> 4 ;
+    const SiTask T = tasks [si_find (tasks, nt, blockIdx.x)] ;
+    const SiSlot S = slots [T.slot] ;
+    const FrontD &f = fr [S.front] ;
+    const i64 ld = f.nsrow ;
+    const int b0 = T.b0, nb = T.nb, b1 = b0 + nb, nR = f.nsrow - b1 ;
+    const int row0 = (blockIdx.x - T.wg0) * 64 ;
+    if (row0 >= nR) return ;
+    double *Mf = M + S.moff ;
+    const double *MR = Mf + b1 + (i64) b1 * ld ;            // Z [R, R]
+    const double *Lb = Lx + f.psx + (i64) b0 * ld ;         // column c of the block: Lb + c ld; L_bb at row b0, L [R, b] at row b1
+    si_d4 acc [4] ;
+#pragma unroll
+    for (int t = 0 ; t < 4 ; t++) acc [t] = (si_d4) {0.0, 0.0, 0.0, 0.0} ;
+    const int ia = min (row0 + 16 * wave + lr, nR - 1) ;
+    for (int kc = 0 ; kc < nR ; kc += SI_KC)
+    {
+        // the chunk's operands of this lane straight from the square, all loads in flight beside the staging of L [R, b]
+        double av [SI_KC / 4] ;
+#pragma unroll
+        for (int u = 0 ; u < SI_KC / 4 ; u++)
+        {
+            const int kk = kc + 4 * u + lk ;
+            av [u] = MR [ia + (i64) min (kk, nR - 1) * ld] ;
+            if (kk >= nR) av [u] = 0.0 ;
+        }
+        __syncthreads () ;
+#pragma unroll
+        for (int q = 0 ; q < SI_KC * 64 / 256 ; q++)
+        {
+            const int k = tid & (SI_KC - 1), c = tid / SI_KC + (256 / SI_KC) * q ;
+            Bs [k * SI_BLD + c] = (kc + k < nR && c < nb) ? Lb [(i64) c * ld + b1 + kc + k] : 0.0 ;
+        }
+        __syncthreads () ;
+#pragma unroll
+        for (int u = 0 ; u < SI_KC / 4 ; u++)
+        {
+            if (kc + 4 * u >= nR) break ;
+#pragma unroll
+            for (int t = 0 ; t < 4 ; t++)
+                acc [t] = __builtin_amdgcn_mfma_f64_16x16x4f64 (av [u], Bs [(4 * u + lk) * SI_BLD + 16 * t + lr], acc [t], 0, 0, 0) ;
+        }
+    }
+    __syncthreads () ;
+    // acc [t][r] of lane (lr, lk) is T (row 16 wave + lk + 4 r, column 16 t + lr)
+#pragma unroll
+    for (int t = 0 ; t < 4 ; t++)
+#pragma unroll
+        for (int r = 0 ; r < 4 ; r++) Ts [16 * wave + lk + 4 * r + SI_TLD * (16 * t + lr)] = acc [t][r] ;
+    for (int e = tid ; e < 64 * 64 ; e += 256)
+    {
+        const int i = e & 63, a = e >> 6 ;
+        Bs [e] = (row0 + i < nR && a < nb) ? Lb [(i64) a * ld + b1 + row0 + i] : 0.0 ;
+    }
+    __syncthreads () ;
+    // the slice's partial P (a, c) = sum_i L (i, a) T (i, c), i ascending; stored [c + 64 a]
+    double *Pt = Pbuf + (T.poff + (blockIdx.x - T.wg0)) * (i64) SI_PTILE ;
+    for (int q = 0 ; q < 16 ; q++)
+    {
+        const int a = wave + 4 * q, c = lane ;
+        double s = 0 ;
+        for (int i = 0 ; i < 64 ; i++) s += Bs [i + 64 * a] * Ts [i + SI_TLD * c] ;
+        Pt [c + 64 * a] = s ;
+    }
+    __syncthreads () ;
+    for (int e = tid ; e < 64 * nb ; e += 256) Bs [e] = Lb [(i64) (e >> 6) * ld + b0 + min (e & 63, nb - 1)] ;       // L_bb: [k + 64 c]
+    __syncthreads () ;
+    if (tid < 64)
+    {
+        for (int c = 0 ; c < nb ; c++) Ts [tid + SI_TLD * c] = -Ts [tid + SI_TLD * c] ;
+        si_row_solve (Ts, SI_TLD, tid, Bs, 64, nb) ;
+    }
+    __syncthreads () ;
+    for (int e = tid ; e < 64 * nb ; e += 256)
+    {
+        const int i = e & 63, c = e >> 6 ;
+        if (row0 + i < nR) Mf [(i64) (b1 + row0 + i) + (i64) (b0 + c) * ld] = Ts [i + SI_TLD * c] ;
+    }
+    for (int e = tid ; e < 64 * 64 ; e += 256)
+    {
+        const int c = e & 63, i = e >> 6 ;
+        if (c < nb && row0 + i < nR) Mf [(i64) (b0 + c) + (i64) (b1 + row0 + i) * ld] = Ts [i + SI_TLD * c] ;
+    }
+}
+
+// Z [b, b] of one block: Q = I + the partials of its slices (added in slice order), Y = Q inv (L_bb) by rows,
+// Z = inv (L_bb)' Y by columns; the lower triangle goes into the square and is mirrored into the upper one.
+__global__ void __launch_bounds__(256) k_si_diag (const SiTask *tasks, const SiSlot *slots, const FrontD *fr,
+    const double *Lx, double *M, const double *Pbuf)
+{
+    extern __shared__ __attribute__ ((aligned (16))) double si_lds [] ;
+    double *Qs = si_lds ;                           // Q (a, c) at [a + SI_TLD c]
+    double *Lbs = si_lds + SI_NB * SI_TLD ;         // L_bb: [k + 64 c]
+    const int tid = threadIdx.x ;
+    const SiTask T = tasks [blockIdx.x] ;
+    const SiSlot S = slots [T.slot] ;
+    const FrontD &f = fr [S.front] ;
+    const i64 ld = f.nsrow ;
+    const int b0 = T.b0, nb = T.nb ;
+    const double *Lbb = Lx + f.psx + (i64) b0 * ld + b0 ;
+    for (int e = tid ; e < SI_PTILE ; e += 256)
+    {
+        const int c = e & 63, a = e >> 6 ;
+        double s = (a == c) ? 1.0 : 0.0 ;
+        for (int q = 0 ; q < T.nslices ; q++) s += Pbuf [(T.poff + q) * (i64) SI_PTILE + e] ;
+        Qs [a + SI_TLD * c] = s ;
+    }
+    for (int e = tid ; e < 64 * nb ; e += 256) Lbs [e] = Lbb [(i64) (e >> 6) * ld + min (e & 63, nb - 1)] ;
+    __syncthreads () ;
+    if (tid < nb) si_row_solve (Qs, SI_TLD, tid, Lbs, 64, nb) ;
+    __syncthreads () ;
+    if (tid < nb) si_col_solve (Qs, SI_TLD, tid, Lbs, 64, nb) ;
+    __syncthreads () ;
+    double *Mf = M + S.moff ;
+    for (int e = tid ; e < SI_PTILE ; e += 256)
+    {
+        const int a = e & 63, c = e >> 6 ;
+        if (a >= nb || c > a) continue ;
+        const double v = Qs [a + SI_TLD * c] ;
+        Mf [(i64) (b0 + a) + (i64) (b0 + c) * ld] = v ;
+        Mf [(i64) (b0 + c) + (i64) (b0 + a) * ld] = v ;
+    }
+}
+
+// the finished panel columns of a front from its square into Zx (the layout of Lx), the dead upper triangle of the
+// diagonal block cleared
+__global__ void __launch_bounds__(256) k_si_store (const SiTask *tasks, int nt, const SiSlot *slots, const FrontD *fr,
+    const double *M, double *Zx)
+{
+    const SiTask T = tasks [si_find (tasks, nt, blockIdx.x)] ;
+    const SiSlot S = slots [T.slot] ;
+    const FrontD &f = fr [S.front] ;
+    const int c = blockIdx.x - T.wg0, ld = f.nsrow ;
+    if (c >= f.nscol) return ;
+    const double *Mc = M + S.moff + (i64) c * ld ;
+    double *Zc = Zx + f.psx + (i64) c * ld ;
+    for (int i = threadIdx.x ; i < ld ; i += 256) Zc [i] = i < c ? 0.0 : Mc [i] ;
+}
+
+// doubles of LDS a thin front needs: M (ncb x ncb), T (ncb x nb), Q (nb x nb), odd leading dimensions
+__host__ __device__ __forceinline__ int si_thin_lds (int nscol, int nsrow)
+{
+    const int ncb = nsrow - nscol ;
+    return (ncb | 1) * (ncb + nscol) + (nscol | 1) * nscol ;
+}
+
+// A thin front (nscol <= SI_NB, nsrow <= SM_MAX) whole: one workgroup, the recurrence above with b = all its columns
+// and R = its below-rows, everything in LDS, L read from the (cached) panel.
+__global__ void __launch_bounds__(256) k_si_thin (const i32 *fronts, const FrontD *fr, const i32 *supermap, const i64 *Ls,
+    const double *Lx, double *Zx)
+{
+    extern __shared__ __attribute__ ((aligned (16))) double si_lds [] ;
+    const int tid = threadIdx.x ;
+    const FrontD &f = fr [fronts [blockIdx.x]] ;
+    const int nb = f.nscol, ld = f.nsrow, ncb = ld - nb, ldm = ncb | 1, ldq = nb | 1 ;
+    double *Ms = si_lds, *Ts = Ms + ldm * ncb, *Qs = Ts + ldm * nb ;
+    const i64 *I = Ls + f.psi + nb ;
+    const double *Lp = Lx + f.psx ;             // L_bb at row 0, L [R, b] at row nb
+    for (int e = tid ; e < ncb * ncb ; e += 256)
+    {
+        const int j = e / ncb, i = e - j * ncb ;
+        if (i < j) continue ;
+        const i64 c = I [j] ;
+        const i64 q = si_locate (fr [supermap [c]], Ls, I [i], c) ;
+        const double v = q >= 0 ? Zx [q] : si_nan () ;
+        Ms [i + ldm * j] = v ; Ms [j + ldm * i] = v ;
+    }
+    __syncthreads () ;
+    for (int e = tid ; e < ncb * nb ; e += 256)
+    {
+        const int c = e / ncb, i = e - c * ncb ;
+        const double *Lc = Lp + (i64) c * ld + nb ;
+        double s = 0 ;
+        for (int k = 0 ; k < ncb ; k++) s += Ms [i + ldm * k] * Lc [k] ;
+        Ts [i + ldm * c] = s ;
+    }
+    __syncthreads () ;
+    for (int e = tid ; e < nb * nb ; e += 256)
+    {
+        const int c = e / nb, a = e - c * nb ;
+        const double *La = Lp + (i64) a * ld + nb ;
+        double s = (a == c) ? 1.0 : 0.0 ;
+        for (int i = 0 ; i < ncb ; i++) s += La [i] * Ts [i + ldm * c] ;
+        Qs [a + ldq * c] = s ;
+    }
+    __syncthreads () ;
+    if (tid < ncb)
+    {
+        for (int c = 0 ; c < nb ; c++) Ts [tid + ldm * c] = -Ts [tid + ldm * c] ;
+        si_row_solve (Ts, ldm, tid, Lp, ld, nb) ;
+    }
+    else if (tid < ncb + nb) si_row_solve (Qs, ldq, tid - ncb, Lp, ld, nb) ;
+    __syncthreads () ;
+    if (tid < nb) si_col_solve (Qs, ldq, tid, Lp, ld, nb) ;
+    __syncthreads () ;
+    double *Zp = Zx + f.psx ;
+    for (int e = tid ; e < ld * nb ; e += 256)
+    {
+        const int c = e / ld, i = e - c * ld ;
+        Zp [e] = i < c ? 0.0 : i < nb ? Qs [i + ldq * c] : Ts [(i - nb) + ldm * c] ;
+    }
+}
+
+// ---- the gather of cholmod_hip_selinv_gather_device ------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(256) k_si_nan_fill (i64 n, double *out)
+{
+    const i64 k = blockIdx.x * (i64) 256 + threadIdx.x ;
+    if (k < n) out [k] = si_nan () ;
+}
+
+// out [src [p]] = Z at the position of entry p of the resident packed S, for the entries S is read at (on or below the
+// diagonal, the last of equal neighbours); the position comes from the supernode map and a search in the row list
+// (d_amap knows the generic fronts only).  One thread per column of S.
+__global__ void __launch_bounds__(256) k_si_gather_values (i64 n, const i64 *Sp, const i64 *Si, const i64 *src,
+    const i32 *supermap, const FrontD *fr, const i64 *Ls, const double *Zx, double *out)
+{
+    const i64 k = blockIdx.x * (i64) 256 + threadIdx.x ;
+    if (k >= n) return ;
+    const FrontD &t = fr [supermap [k]] ;
+    const i64 pend = Sp [k + 1] ;
+    for (i64 p = Sp [k] ; p < pend ; p++)
+    {
+        const i64 i = Si [p] ;
+        if (i < k || i >= n || (p + 1 < pend && Si [p + 1] == i)) continue ;
+        const i64 q = si_locate (t, Ls, i, k) ;
+        if (q >= 0) out [src [p]] = Zx [q] ;
+    }
+}
+
+// out [perm ? perm [k] : k] = Z (k, k)
+__global__ void __launch_bounds__(256) k_si_gather_diag (i64 n, const i64 *perm, const i32 *supermap, const FrontD *fr,
+    const double *Zx, double *out)
+{
+    const i64 k = blockIdx.x * (i64) 256 + threadIdx.x ;
+    if (k >= n) return ;
+    const FrontD &t = fr [supermap [k]] ;
+    const i64 jc = k - t.k1 ;
+    out [perm ? perm [k] : k] = Zx [t.psx + jc * (i64) t.nsrow + jc] ;
+}
+
+} // namespace sship

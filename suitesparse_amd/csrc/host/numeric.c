@@ -572,6 +572,8 @@ static uint64_t pattern_hash (cholmod_sparse *A, uint64_t *second)
  *     team 1:    thread 0 does all four in that order.
  * Returns what cholmod_l_factorize returns, or -1: take the long way -- hash [0 .. 1] then holds A's pattern hash and L
  * no longer claims a factor on the device. */
+uint64_t ssamd_pattern_hash (cholmod_sparse *A, uint64_t *second) { return pattern_hash (A, second) ; }
+
 static int factorize_values_only (cholmod_sparse *A, double beta, cholmod_factor *L, cholmod_common *Common, uint64_t hash [2])
 {
     cholmod_hip_plan *plan = (cholmod_hip_plan *) L->hip_plan ;
