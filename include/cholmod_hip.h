@@ -73,6 +73,12 @@ extern "C" {
                                          * columns (rotations of the even ones) on the way into LDS / registers.  One
                                          * rank, generic kernels only (no thin-front kernels).  cholmod_hip_download_factor
                                          * then returns the complex factor itself */
+#define CHOLMOD_HIP_FUSED_CB_EA   65536    /* one GPU, real fronts: the update that first writes the whole contribution block of a
+                                         * front also adds the children's entries that land there (k_update3f, through inverse
+                                         * relative maps built once per plan), and the second extend-add phase leaves those
+                                         * columns out: 16 B less traffic per child entry.  The factor changes by rounding at
+                                         * most.  Set by cholmod_l_super_numeric unless CHOLMOD_HIP_NO_FUSED_CB_EA=1 is in the
+                                         * environment; without it a plan is what it was before the flag existed */
 #define CHOLMOD_HIP_PLAN_HOST_ONLY 2    /* build the schedule only, touch no device
                                            (CPU-side tests of the host logic)       */
 
@@ -161,6 +167,16 @@ int64_t cholmod_hip_debug_routing (cholmod_hip_plan *plan, int64_t cap, int64_t 
     int64_t *cb_lo, int64_t *cb_hi) ;
 /* test hook: fingerprint (16 words) of the rank's plan -- fronts, routing, layout, every group array, the launch list */
 int cholmod_hip_debug_schedule_hash (cholmod_hip_plan *plan, uint64_t *out16) ;
+/* test hooks (plans with CHOLMOD_HIP_FUSED_CB_EA).  cholmod_hip_debug_cb_extend_add: per front 4 numbers -- [0] 1 if it is a
+ * generic front with children and a contribution block, [1] regions that take the contribution-block half of its
+ * extend-add with them, [2] extend-add groups that cover its contribution-block columns, [3] its children; returns nsuper,
+ * fills at most cap fronts.  cholmod_hip_debug_fused_pair: (parent, child) pair `pair` of those regions -- desc [8] = parent,
+ * child, columns of the parent, rows of its contribution block, rows of the child's, 1 if the child's block is a packed
+ * triangle, child rows that land in the parent's block, launch that holds the region; inv (rows of the parent's block) and
+ * rel (rows of the child's) receive, if not NULL and the plan is on a device, the pair's inverse and relative map as the
+ * device holds them.  Returns the number of pairs. */
+int64_t cholmod_hip_debug_cb_extend_add (cholmod_hip_plan *plan, int64_t cap, int64_t *out) ;
+int64_t cholmod_hip_debug_fused_pair (cholmod_hip_plan *plan, int64_t pair, int64_t *desc, int32_t *inv, int32_t *rel) ;
 /* Progress of the factorization that is running (or ran last) on this plan, for a watchdog thread of the caller (bench.py
  * --gpus N: a hung collective must end in an error line, not in the driver's kill).  cholmod_hip_progress_enable (plan, 1)
  * allocates two words of pinned host memory the device marks, in stream order, around every block-column exchange.

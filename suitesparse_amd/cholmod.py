@@ -33,6 +33,7 @@ HIP_PLAN_HOST_ONLY = 2
 # plan flags (include/cholmod_hip.h)
 HIP_WIDE_OB, HIP_NO_FUSED_POTRF, HIP_NO_FUSED_TRSM, HIP_PHI_TWIN = 128, 512, 1024, 16384
 HIP_NO_SMALL_FRONTS = 16
+HIP_FUSED_CB_EA = 65536
 HIP_OK = 0
 HIP_INVALID = -4
 HIP_NO_DEVICE = -1
@@ -165,6 +166,7 @@ HIP_SYMBOLS = [
     "cholmod_hip_selinv_device", "cholmod_hip_selinv_gather_device", "cholmod_hip_selinv_download",
     "cholmod_hip_selinv_release", "cholmod_hip_selinv_info",
     "cholmod_hip_dense_partial_factor", "cholmod_hip_factor_checks", "cholmod_hip_factor_checks_local", "cholmod_hip_get_launch_profile", "cholmod_hip_debug_thin_cycles", "cholmod_hip_debug_launch_regions",
+    "cholmod_hip_debug_cb_extend_add", "cholmod_hip_debug_fused_pair",
     "cholmod_hip_rccl_unique_id", "cholmod_hip_rccl_attach", "cholmod_hip_rccl_detach",
     "cholmod_hip_version",
 ]
@@ -318,6 +320,8 @@ def lib(hooks=None):
     sig("cholmod_hip_get_launch_profile", i64, [vp, i64, vp, vp, vp, vp, vp, vp])
     sig("cholmod_hip_debug_thin_cycles", C.c_int, [vp, i64, vp])
     sig("cholmod_hip_debug_launch_regions", i64, [vp, i64, i64, vp])
+    sig("cholmod_hip_debug_cb_extend_add", i64, [vp, i64, vp])
+    sig("cholmod_hip_debug_fused_pair", i64, [vp, i64, vp, vp, vp])
     sig("cholmod_hip_rccl_unique_id", C.c_int, [vp])
     sig("cholmod_hip_rccl_attach", C.c_int, [vp, vp])
     sig("cholmod_hip_rccl_detach", C.c_int, [vp])

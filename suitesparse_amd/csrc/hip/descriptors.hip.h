@@ -96,6 +96,17 @@ struct GemmGroup {
 // map [j] ldc]; its columns are the first g.n entries of the same list (the region starts on the diagonal, g.tri = 1).
 struct GatherGroup { GemmGroup g; i64 map; i32 tile_start; i32 pad; };
 
+// The contribution-block half of the extend-add fused into an update (plans with CHOLMOD_HIP_FUSED_CB_EA; schedule_dense.hip:
+// the carrier of a front).  The one region that covers the whole contribution block of a front also takes the children's
+// entries that land there: FuseD names the children (entries cd0 .. cd0 + nch of the child lists, hence of the ChildD array)
+// and their INVERSE maps -- child c's at inv + c ncb in the plan's inverse-map array: parent contribution-block row -> child
+// contribution-block row, or -1 (k_invmap builds them from the relative maps once per plan).  A side array of the
+// schedule next to the regions (Schedule::fz, ::gfz), not part of GemmGroup.
+struct FuseD { i64 inv ; i32 front ; i32 cd0 ; i32 nch ; i32 ncb ; } ;
+// one (parent, child) pair of a FuseD: where its relative map lies, where its inverse map goes
+// (mcb: how many of the child's nc rows land in the parent's contribution block -- its last mcb rows)
+struct InvPair { i64 rel ; i64 inv ; i32 nc ; i32 pnscol ; i32 pncb ; i32 parent ; i32 child ; i32 mcb ; } ;
+
 // Contribution blocks of the generic fronts are stored as full squares, ld = ncb
 // (lower part used); those of the thin fronts as packed lower triangles:
 // element (i,j), i >= j, of a packed triangle of order m lives at tri_col(j,m) + i.

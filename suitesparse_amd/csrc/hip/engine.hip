@@ -35,7 +35,7 @@ static void free_device (cholmod_hip_plan *P)
         P->d_lvl_list, P->d_Lx, P->d_cb, P->d_zg, P->d_eg, P->d_pg, P->d_tg, P->d_tu_cnt, P->d_cdesc, P->d_smd, P->d_sp01, P->d_gg, P->d_sm,
         P->d_Sp, P->d_Si, P->d_Snz, P->d_Sx, P->d_amap, P->d_X, P->d_perm, P->d_xchg, P->d_stage, P->d_ag, P->d_agf, P->d_Lx_full, P->d_fr_full, P->d_dg, P->d_rg, P->d_wg, P->d_cg, P->d_cflags, P->d_crel, P->d_relpairs, P->d_dinv, P->d_sv,
         P->d_inv_tasks, P->d_winv, P->d_solved, P->d_sv_acc, P->d_sd_W, P->d_sd_acc, P->d_chk, P->d_chk_out, P->d_thin_tim, P->d_sb_tasks, P->d_sb_commit, P->d_first_fail, P->d_vsrc, P->d_vals,
-        P->d_xg, P->d_gmap, P->d_rs_Tp, P->d_rs_Tj, P->d_rs_Tq, P->d_rs_X, P->d_rs_B} ;
+        P->d_xg, P->d_gmap, P->d_fz, P->d_gfz, P->d_invmap, P->d_rs_Tp, P->d_rs_Tj, P->d_rs_Tq, P->d_rs_X, P->d_rs_B} ;
     for (void *p : ptrs) if (p) (void) hipFree (p) ;
     for (auto e : P->evpool) (void) hipEventDestroy (e) ;
     for (auto e : P->sync_ev) (void) hipEventDestroy (e) ;
@@ -89,7 +89,7 @@ static int upload_plan (cholmod_hip_plan *P)
     size_t freeb = 0, totalb = 0 ;
     HIPCHK (hipMemGetInfo (&freeb, &totalb)) ;
     double need = 8.0 * P->lx_local + 8.0 * P->arena + 8.0 * P->ssize + 4.0 * P->relsize
-        + sizeof (GemmGroup) * (double) P->sch.gg.size () + 64.0 * P->nsuper + (double) (64 << 20) ;
+        + sizeof (GemmGroup) * (double) P->sch.gg.size () + 64.0 * P->nsuper + (double) (64 << 20) + 4.0 * P->sch.invsize ;
     if (need > (double) freeb)
     {
         fprintf (stderr, "cholmod_hip: factor needs %.2f GB of HBM, %.2f GB free\n",
@@ -126,6 +126,15 @@ static int upload_plan (cholmod_hip_plan *P)
     P->d_cg = dupload (P->sch.cg, e) ; HIPCHK (e) ;
     P->d_xg = dupload (P->sch.xg, e) ; HIPCHK (e) ;
     P->d_gmap = dupload (P->sch.gmap, e) ; HIPCHK (e) ;
+    if (!P->sch.fz.empty ())
+    {
+        // (the regions that carry their children's contribution-block entries: one entry per region of the schedule)
+        std::vector<i32> gfz (P->sch.gfz) ;
+        gfz.resize (P->sch.gg.size (), -1) ;
+        P->d_fz = dupload (P->sch.fz, e) ; HIPCHK (e) ;
+        P->d_gfz = dupload (gfz, e) ; HIPCHK (e) ;
+        HIPCHK (hipMalloc ((void **) &P->d_invmap, std::max<i64> (P->sch.invsize, 1) * sizeof (i32))) ;
+    }
     HIPCHK (hipMalloc ((void **) &P->d_cflags, (4 * (size_t) P->sch.ncflags + 4) * sizeof (int))) ;
     HIPCHK (hipMalloc ((void **) &P->d_dinv, (size_t) std::max (P->sch.max_dinv_slots, 1) * 4096 * sizeof (double))) ;
     P->d_sm = dupload (P->sch.sm, e) ; HIPCHK (e) ;
@@ -174,8 +183,15 @@ static int upload_plan (cholmod_hip_plan *P)
         if (!P->relpairs.empty ())
             hipLaunchKernelGGL (k_relmap_pairs, dim3 ((unsigned) ((P->relpairs.size () * 64 + 255) / 256)), dim3 (256), 0, P->stream,
                 (int) P->relpairs.size (), P->d_relpairs, P->d_fr, P->d_Ls, P->d_relmap) ;
-        HIPCHK (hipGetLastError ()) ;
-        HIPCHK (hipStreamSynchronize (P->stream)) ;
+        InvPair *d_ivp = nullptr ;
+        if (!P->sch.ivp.empty ())
+        {
+            d_ivp = dupload (P->sch.ivp, e) ;
+            if (e == hipSuccess) hipLaunchKernelGGL (k_invmap, dim3 ((unsigned) P->sch.ivp.size ()), dim3 (256), 0, P->stream, d_ivp, P->d_relmap, P->d_invmap) ;
+        }
+        hipError_t e1 = hipGetLastError (), e2 = hipStreamSynchronize (P->stream) ;
+        if (d_ivp) (void) hipFree (d_ivp) ;
+        HIPCHK (e) ; HIPCHK (e1) ; HIPCHK (e2) ;
     }
     if (ptiming) fprintf (stderr, "cholmod_hip upload_plan: streams/events %.3f s, maps + schedule H2D %.3f s, hipMalloc (L %.1f GB, arena %.1f GB) %.3f s, relmap kernel %.3f s\n",
         tu1 - tu0, tu2 - tu1, 8e-9 * P->lx_local, 8e-9 * P->arena, tu3 - tu2, pnow () - tu3) ;
@@ -350,6 +366,18 @@ static int run_launch (cholmod_hip_plan *P, const Launch &L, bool serial)
                 const unsigned g4 = (unsigned) (((L.grid + 31) / 32) * 8) ;
                 if (L.aux >= 1024) TW_LAUNCH (k_update3<4 COMMA, COMMA 4>, dim3 (g4), dim3 (256), 0, st, P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
                 else TW_LAUNCH (k_update3<2 COMMA, COMMA 4>, dim3 (g4), dim3 (256), 0, st, P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
+            }
+            else if (L.fused)
+            {
+                // a region of the launch takes its children's contribution-block entries with it (k_update3f; one GPU, real)
+                if (!P->d_fz || cx || twin) { fprintf (stderr, "cholmod_hip: a fused update launch without its side arrays\n") ; return CHOLMOD_HIP_INVALID ; }
+                const unsigned gh = 2u * (unsigned) ((L.grid + 7) / 8 * 8) ;
+#define UPD3F_ARGS P->d_gg + L.goff, L.ng, P->d_gfz + L.goff, P->d_fz, P->d_cdesc, P->d_invmap, P->d_Lx, P->d_cb
+                if (L.half && L.aux >= 1024) hipLaunchKernelGGL ((k_update3f<4, true>), dim3 (gh), dim3 (64), 0, st, UPD3F_ARGS) ;
+                else if (L.half) hipLaunchKernelGGL ((k_update3f<2, true>), dim3 (gh), dim3 (64), 0, st, UPD3F_ARGS) ;
+                else if (L.aux >= 1024) hipLaunchKernelGGL ((k_update3f<4, false>), dim3 (L.grid), dim3 (64), 0, st, UPD3F_ARGS) ;
+                else hipLaunchKernelGGL ((k_update3f<2, false>), dim3 (L.grid), dim3 (64), 0, st, UPD3F_ARGS) ;
+#undef UPD3F_ARGS
             }
             else if (L.half)
             {
@@ -1474,6 +1502,13 @@ int cholmod_hip_debug_schedule_hash (cholmod_hip_plan *P, uint64_t *out16)
     out16 [4] = hv (S.gg) ;
     // (gathered head regions and their row maps: folded in only where a plan has them, so plans without heads hash as before)
     if (!S.xg.empty ()) out16 [4] = fnv (fnv (out16 [4], S.xg.data (), S.xg.size () * sizeof (GatherGroup)), S.gmap.data (), S.gmap.size () * sizeof (i32)) ;
+    // (likewise the regions that carry their children's contribution-block entries, their list by region and their pairs)
+    if (!S.fz.empty ())
+    {
+        const i64 w [] = {(i64) S.invsize, (i64) S.gfz.size ()} ;
+        out16 [4] = fnv (fnv (fnv (fnv (out16 [4], S.fz.data (), S.fz.size () * sizeof (FuseD)), S.gfz.data (), S.gfz.size () * sizeof (i32)),
+            S.ivp.data (), S.ivp.size () * sizeof (InvPair)), w, sizeof (w)) ;
+    }
     out16 [5] = hv (S.dg) ; out16 [6] = hv (S.rg) ; out16 [7] = hv (S.wg) ;
     out16 [8] = hv (S.cg) ; out16 [9] = hv (S.sm) ;
     uint64_t h = H0 ;
@@ -1493,6 +1528,45 @@ int cholmod_hip_debug_schedule_hash (cholmod_hip_plan *P, uint64_t *out16)
     out16 [14] = fnv (H0, w, sizeof (w)) ;
     out16 [15] = fnv (fnv (hv (P->lpx), P->win_off.data (), P->win_off.size () * sizeof (i64)), P->assign_cb.data (), P->assign_cb.size ()) ;
     return CHOLMOD_HIP_OK ;
+}
+
+int64_t cholmod_hip_debug_cb_extend_add (cholmod_hip_plan *P, int64_t cap, int64_t *out)
+{
+    if (!P || !out) return CHOLMOD_HIP_INVALID ;
+    const Schedule &S = P->sch ;
+    std::vector<i64> v (4 * (size_t) std::max<i64> (P->nsuper, 1), 0) ;
+    for (i64 s = 0 ; s < P->nsuper ; s++)
+    {
+        const FrontD &f = P->fr [s] ;
+        v [4 * s] = (!f.cbp && f.ncb > 0 && f.child_end > f.child_begin) ? 1 : 0 ;
+        v [4 * s + 3] = f.child_end - f.child_begin ;
+    }
+    for (const FuseD &Z : S.fz) v [4 * (size_t) Z.front + 1]++ ;
+    for (const EaGroup &E : S.eg) if (E.c_lo <= P->fr [E.front].nscol && E.c_hi == P->fr [E.front].nsrow && P->fr [E.front].ncb > 0) v [4 * (size_t) E.front + 2]++ ;
+    for (i64 s = 0 ; s < P->nsuper && s < cap ; s++) for (int t = 0 ; t < 4 ; t++) out [4 * s + t] = v [4 * s + t] ;
+    return P->nsuper ;
+}
+
+int64_t cholmod_hip_debug_fused_pair (cholmod_hip_plan *P, int64_t pair, int64_t *desc, int32_t *inv, int32_t *rel)
+{
+    if (!P) return CHOLMOD_HIP_INVALID ;
+    const Schedule &S = P->sch ;
+    const i64 np = (i64) S.ivp.size () ;
+    if (pair < 0 || pair >= np || !desc) return np ;
+    const InvPair &R = S.ivp [pair] ;
+    i64 launch = -1 ;
+    for (size_t z = 0 ; z < S.fz.size () && launch < 0 ; z++)
+    {
+        if (S.fz [z].front != R.parent) continue ;
+        const size_t q = (size_t) (std::find (S.gfz.begin (), S.gfz.end (), (i32) z) - S.gfz.begin ()) ;
+        for (size_t l = 0 ; l < S.launches.size () ; l++)
+            if (S.launches [l].kind == K_UPD_W && q >= S.launches [l].goff && q < S.launches [l].goff + S.launches [l].ng) launch = (i64) l ;
+    }
+    const i64 d [8] = {R.parent, R.child, R.pnscol, R.pncb, R.nc, P->fr [R.child].cbp, R.mcb, launch} ;
+    for (int t = 0 ; t < 8 ; t++) desc [t] = d [t] ;
+    if (inv && P->d_invmap) HIPCHK (hipMemcpy (inv, P->d_invmap + R.inv, (size_t) R.pncb * sizeof (i32), hipMemcpyDeviceToHost)) ;
+    if (rel && P->d_relmap) HIPCHK (hipMemcpy (rel, P->d_relmap + R.rel, (size_t) R.nc * sizeof (i32), hipMemcpyDeviceToHost)) ;
+    return np ;
 }
 
 // tuning: the update regions of launch `launch` (an update launch of any kind), 12 numbers per

@@ -80,6 +80,22 @@ __global__ void __launch_bounds__(256) k_relmap_pairs (int npairs, const RelPair
     }
 }
 
+// For the (parent, child) pairs whose contribution-block entries ride with an update (InvPair; update_tile_w:
+// FUSE), the inverse restricted to the parent's contribution block: inv [t] = the child row that lands on row t of the
+// parent's contribution block, -1: none.  One workgroup per pair; run once per plan, behind k_relmap.
+__global__ void __launch_bounds__(256) k_invmap (const InvPair *pr, const i32 *relmap, i32 *invmap)
+{
+    const InvPair R = pr [blockIdx.x] ;
+    i32 *inv = invmap + R.inv ;
+    for (int t = threadIdx.x ; t < R.pncb ; t += 256) inv [t] = -1 ;
+    __syncthreads () ;
+    for (int j = threadIdx.x ; j < R.nc ; j += 256)
+    {
+        const int t = relmap [R.rel + j] - R.pnscol ;
+        if (t >= 0 && t < R.pncb) inv [t] = j ;
+    }
+}
+
 // ---- assemble A into the panels ---------------------------------------------
 // reference: t_cholmod_super_numeric.c:353-431 (ASSIGN semantics, entries not
 // in the symbolic pattern are dropped, beta added to the diagonal).
@@ -1872,11 +1888,21 @@ __global__ void __launch_bounds__(256, MINW) k_update2 (const GemmGroup *g, int 
 // pairs and the epilogue's rows and columns are looked up in the region's row map once per tile; the k-loop, its loads and the
 // MFMA order are those of the plain tile (every pair of the map is a pair of adjacent rows of the front), so an entry the
 // gathered tile computes is bit for bit what the plain tile computes there.
-template <int DEPTH, bool EDGE, int TW = 0, int NQ = 2, bool GATHER = false>
+// FUSE (k_update3f): the region may be the CARRIER of its front (schedule_dense.hip; fz != nullptr) -- the one update that
+// covers the front's whole contribution block and is the first to write all of it.  Between the k-loop and the epilogue
+// the children's entries that land in this tile are then taken off the accumulators, child by child in the order of the child
+// list: the lane looks its 4 rows and 8 NQ columns up in the child's inverse map (parent contribution-block row -> child
+// row, -1: none; monotone, so row >= column in the parent is row >= column in the child) and loads the entries that exist,
+// lower triangle only, from the child's full square or packed triangle with plain 8-byte loads.  The epilogue is the plain
+// one: C = -(acc - c1 - c2 ...) where it assigns -- bit for bit what the assigning update followed by the extend-add of
+// c1, c2, ... gives -- and C -= (acc - c1 - c2 ...) where it updates.  A child without a row or without a column in the
+// tile costs one map lookup; a tile no child touches, and every region that is no carrier, runs as in k_update3.
+template <int DEPTH, bool EDGE, int TW = 0, int NQ = 2, bool GATHER = false, bool FUSE = false>
 __device__ __forceinline__ void update_tile_w (const GemmGroup &G, int I, int J, double *Lx, double *CB, int cofs = 0,
-    const i32 *rmap = nullptr)
+    const i32 *rmap = nullptr, const FuseD *fz = nullptr, const ChildD *cdesc = nullptr, const i32 *invmap = nullptr)
 {
     static_assert (!GATHER || (TW == 0 && !UPD3_CLAMP_LOADS), "a gathered tile is real and loads row pairs") ;
+    static_assert (!FUSE || (TW == 0 && !GATHER), "a carrier is a real, plain region") ;
     const int lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4 ;
     const int row0 = I * 64, col0 = J * 64 + cofs ;
     const int mrem = G.m - row0, nrem = G.n - col0 ;
@@ -2025,6 +2051,46 @@ __device__ __forceinline__ void update_tile_w (const GemmGroup &G, int I, int J,
                     acc [2 * q + 1][2 * p][r] = oe ; acc [2 * q][2 * p + 1][r] = -oe ;
                 }
     }
+    if constexpr (FUSE)
+    {
+        if (fz)
+        {
+            const FuseD Z = *fz ;
+            for (int c = 0 ; c < Z.nch ; c++)
+            {
+                const i32 *im = invmap + Z.inv + (i64) c * Z.ncb ;
+                int ri [2][2] ;
+                bool any = false ;
+#pragma unroll
+                for (int q = 0 ; q < 2 ; q++)
+#pragma unroll
+                    for (int h = 0 ; h < 2 ; h++)
+                    {
+                        const int i = row0 + 32 * q + 2 * lr + h ;
+                        ri [q][h] = i < G.m ? im [i] : -1 ;
+                        any = any || ri [q][h] >= 0 ;
+                    }
+                if (!__any (any)) continue ;            // (the child has no row in this tile)
+                const ChildD D = cdesc [Z.cd0 + c] ;
+                const double *src = CB + D.cb ;
+#pragma unroll
+                for (int b = 0 ; b < 2 * NQ ; b++)
+#pragma unroll
+                    for (int r = 0 ; r < 4 ; r++)
+                    {
+                        const int j = col0 + 32 * (b >> 1) + 2 * (lk + 4 * r) + (b & 1) ;
+                        const int cj = j < G.n ? im [j] : -1 ;
+                        if (cj < 0) continue ;
+                        const i64 coff = (i64) cj * D.ncb - (D.cbp ? (((i64) cj * (cj + 1)) >> 1) : 0) ;
+#pragma unroll
+                        for (int q = 0 ; q < 2 ; q++)
+#pragma unroll
+                            for (int h = 0 ; h < 2 ; h++)
+                                if (ri [q][h] >= cj) acc [2 * q + h][b][r] -= src [coff + ri [q][h]] ;
+                    }
+            }
+        }
+    }
     // epilogue: acc [a][b][r] of lane (lr, lk) is C (row 32 (a >> 1) + 2 lr + (a & 1),
     // column 32 (b >> 1) + 2 (lk + 4 r) + (b & 1))
     double *C = (G.c_in_cb ? CB : Lx) + G.c_off + row0 + colx<TW == 2> (col0, G.ldc) ;
@@ -2113,6 +2179,35 @@ __global__ void __launch_bounds__(64 * WPB, 2) k_update3 (const GemmGroup *g, in
     {
         if (G.m - I * 64 >= 64 && G.n - J * 64 >= 64) update_tile_w<DEPTH, false, TW> (G, I, J, Lx, CB) ;
         else update_tile_w<DEPTH, true, TW> (G, I, J, Lx, CB) ;
+    }
+}
+
+// k_update3 for a launch that holds a carrier (update_tile_w: FUSE): gfz [q] = the FuseD of region q of the launch, -1: the
+// region is a plain one.  Real plans on one GPU only: whole tiles or HALF tiles, one per workgroup.
+template <int DEPTH, bool HALF = false>
+__global__ void __launch_bounds__(64, 2) k_update3f (const GemmGroup *g, int ng, const i32 *gfz, const FuseD *fzs, const ChildD *cdesc,
+    const i32 *invmap, double *Lx, double *CB)
+{
+    int vb = (int) blockIdx.x ;
+    int cofs = 0 ;
+    if constexpr (HALF) { cofs = ((vb >> 3) & 1) * 32 ; vb = ((vb >> 4) << 3) | (vb & 7) ; }
+    const int gi = find_group (g, ng, vb, &GemmGroup::tile_start) ;
+    GemmGroup G = g [gi] ;
+    const int z = gfz [gi] ;
+    const FuseD *fz = z >= 0 ? fzs + z : nullptr ;
+    int I, J ;
+    if (vb - G.tile_start >= G.nblk) return ;
+    if (!decode_tile (G, vb - G.tile_start, I, J)) return ;
+    if constexpr (HALF)
+    {
+        if (G.n - J * 64 - cofs <= 0) return ;
+        if (G.m - I * 64 >= 64 && G.n - J * 64 - cofs >= 32) update_tile_w<DEPTH, false, 0, 1, false, true> (G, I, J, Lx, CB, cofs, nullptr, fz, cdesc, invmap) ;
+        else update_tile_w<DEPTH, true, 0, 1, false, true> (G, I, J, Lx, CB, cofs, nullptr, fz, cdesc, invmap) ;
+    }
+    else
+    {
+        if (G.m - I * 64 >= 64 && G.n - J * 64 >= 64) update_tile_w<DEPTH, false, 0, 2, false, true> (G, I, J, Lx, CB, 0, nullptr, fz, cdesc, invmap) ;
+        else update_tile_w<DEPTH, true, 0, 2, false, true> (G, I, J, Lx, CB, 0, nullptr, fz, cdesc, invmap) ;
     }
 }
 

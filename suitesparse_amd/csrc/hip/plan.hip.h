@@ -99,6 +99,7 @@ struct Launch {
     int ndiag = 0 ;                 // K_CHAINF: diagonal workgroups of the launch (they come first in the grid)
     int half = 0 ;                  // K_UPD_W: two waves per 64 x 64 tile, 64 x 32 each (k_update3<..., HALF>): launches of 512 .. 10 240 tiles
     double skipped = 0 ;            // K_UPD_G: algorithmic flops of the rows the heads do not reach (not executed)
+    int fused = 0 ;                 // K_UPD_W: a region of the launch takes its children's contribution-block entries (k_update3f)
 } ;
 
 #define HIPCHK(call) do { hipError_t e_ = (call) ; if (e_ != hipSuccess) { \
@@ -187,6 +188,10 @@ struct Schedule {
     std::vector<CfGroup> cg ;       // k_chainf: the 256-column chain in one launch (diagonal + row workgroups, flags)
     std::vector<GatherGroup> xg ;   // k_update3g: head updates restricted to the rows their heads reach
     std::vector<i32> gmap ;         // ... their row maps (GatherGroup::map indexes this)
+    std::vector<FuseD> fz ;         // regions that take the contribution-block half of their front's extend-add (FuseD) ...
+    std::vector<i32> gfz ;          // ... by region: gfz [q] = entry of fz that goes with gg [q], -1: none (empty, or as long as gg)
+    std::vector<InvPair> ivp ;      // ... and their (parent, child) pairs, in the order of the inverse maps
+    i64 invsize = 0 ;               // ... whose total length this is (i32 entries)
     int ncflags = 0 ;               // flag slots (one per front and sub-block column of the whole schedule)
     int max_dinv_slots = 0 ;        // most diagonal sub-blocks in one launch (size of the inverse buffer)
     std::vector<i32> sm ;           // front ids handled by the fused small-front kernel
@@ -298,6 +303,8 @@ struct cholmod_hip_plan {
     std::vector<i32> reach_first, head ;
     bool head_gather = true ;               // the head update over the rows it reaches only (CHOLMOD_HIP_HEAD_NO_GATHER: all rows)
     GatherGroup *d_xg = nullptr ; i32 *d_gmap = nullptr ;
+    // the contribution-block half of the extend-add fused into the updates (CHOLMOD_HIP_FUSED_CB_EA; Schedule::fz, gfz, ivp)
+    FuseD *d_fz = nullptr ; i32 *d_gfz = nullptr, *d_invmap = nullptr ;
     // device
     hipStream_t stream = nullptr ;          // main stream
     hipStream_t stream2 = nullptr ;         // exchange stream (exchange look-ahead of a shared front's next block column)
@@ -424,6 +431,6 @@ int build_host (cholmod_hip_plan *P) ;
 void schedule_dense (const std::vector<FrontD> &fr, const i32 *ids, int nf,
     Schedule &S, int flags, const i32 *owner, const i32 *grp0, const i32 *grpn, int rank, int world,
     const char *assign_cb = nullptr, const i64 *win = nullptr, const i32 *child = nullptr, bool allow_half = false,
-    const HeadInfo *heads = nullptr) ;
+    const HeadInfo *heads = nullptr, const i64 *crel = nullptr, const std::vector<i64> *Ls = nullptr) ;
 
 } // namespace sship

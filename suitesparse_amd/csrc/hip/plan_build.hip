@@ -710,8 +710,9 @@ struct PlanBuilder
         if (Lz.ng) S.launches.push_back (Lz) ;
     }
     // extend-add of the generic fronts of a batch.  phase 0 (before the dense phase): everything into the panel columns, and
-    // into the CB columns of the zero-filled fronts; phase 1 (after it): the CB columns of the assign fronts
-    void schedule_extend_add (const i32 *ids, int nf, int phase)
+    // into the CB columns of the zero-filled fronts; phase 1 (after it): the CB columns of the assign fronts -- but for the
+    // fronts in `fused`, whose carrier update has taken that half with it (schedule_dense.hip: the carrier of a front)
+    void schedule_extend_add (const i32 *ids, int nf, int phase, const std::vector<char> *fused = nullptr)
     {
         Schedule &S = P->sch ;
         Launch Le {K_EA, 0, 0, S.eg.size (), 0, 0} ;
@@ -732,7 +733,7 @@ struct PlanBuilder
             // enters the window: schedule_dense, emit_win)
             int lo = (phase == 0 && !f.own_w) ? 0 : f.nscol ;
             int hi = phase == 0 ? (asg ? f.nscol : f.nsrow) : f.nsrow ;
-            if (phase == 1 && !asg) continue ;
+            if (phase == 1 && (!asg || (fused && (*fused) [q]))) continue ;
             if (hi <= lo) continue ;
             S.eg.push_back (EaGroup {ids [q], blocks, lo, hi, EA_NO_PBASE}) ;
             blocks += (hi - lo + tw - 1) / tw ;
@@ -762,12 +763,26 @@ struct PlanBuilder
             const int nf = (int) gen.size () ;
             if (nf == 0) continue ;
             schedule_zero (ids, nf) ;
+            const size_t ea0 = S.launches.size (), fz0 = S.fz.size (), ivp0 = S.ivp.size () ;
             schedule_extend_add (ids, nf, 0) ;
+            const bool has_ea0 = S.launches.size () > ea0 ;
             schedule_dense (P->fr, ids, nf, S, P->flags, P->owner.data (), P->grp0.data (), P->grpn.data (),
                 P->rank, P->world, P->assign_cb.data (), P->win_off.data (), P->child.data (),
                 P->world == 1 && !P->force_shared,        // (half tiles: one GPU -- plans of several ranks run four tiles per workgroup)
-                P->head.empty () ? nullptr : &heads) ;
-            schedule_extend_add (ids, nf, 1) ;
+                P->head.empty () ? nullptr : &heads, P->crel.data (), &P->Ls) ;
+            if (S.fz.size () == fz0) { schedule_extend_add (ids, nf, 1) ; continue ; }
+            // fronts whose carrier took the contribution-block half of their extend-add: out of the second phase, and what
+            // the first phase was priced at for both (24 B per child entry) less the entries that no longer go through it
+            std::vector<char> fused (nf, 0) ;
+            {
+                std::map<i32, int> at ;
+                for (int q = 0 ; q < nf ; q++) at [ids [q]] = q ;
+                for (size_t z = fz0 ; z < S.fz.size () ; z++) fused [at [S.fz [z].front]] = 1 ;
+            }
+            if (has_ea0)
+                for (size_t z = ivp0 ; z < S.ivp.size () ; z++)
+                    S.launches [ea0].bytes -= 24.0 * ((double) S.ivp [z].mcb * (S.ivp [z].mcb + 1) / 2) ;
+            schedule_extend_add (ids, nf, 1, &fused) ;
         }
     }
 

@@ -36,6 +36,8 @@ struct DenseScheduler
     const i32 *child ;              // the rank's child lists (pricing of the extend-add into a window)
     const bool allow_half ;         // one GPU: launches of a few thousand tiles may run two waves per tile (below)
     const HeadInfo *heads ;         // heads of the fronts (one GPU, real plans; nullptr: none)
+    const i64 *crel ;               // per entry of the child lists: offset of that pair's relative map
+    const std::vector<i64> *Ls ;    // row lists of the fronts (pricing of the fused extend-add)
     // ---- derived once per batch
     // The real twin of a complex factor (phi embedding, host/complex.c): every row / column pair (2i, 2i+1) is (re, im) of
     // one complex row, the odd columns of a panel are the rotations of the even ones.  The update kernels then contract over
@@ -81,12 +83,21 @@ struct DenseScheduler
     std::vector<int> early_open ;           // block column of front q opened (window) ahead of time
     std::vector<int> pf_done ;              // column whose diagonal block a fused update / solve has factored
     std::vector<Upd> step ;
+    // The contribution-block half of the extend-add, fused (CHOLMOD_HIP_FUSED_CB_EA; one GPU, real fronts nobody shares, with
+    // an assigned contribution block and children): ONE region of the front covers its whole contribution block and is
+    // the first to write all of it -- the assigning first outer update, or, on a front with a head, the outer update right
+    // behind the head (the head update itself, gathered or not, stays what it is: both forms of it keep giving the same
+    // factor bit for bit).  That region is the front's CARRIER: where it goes to the one-wave kernel (flush_kind, K_UPD_W) it
+    // takes the children's entries with it (descriptors.hip.h: FuseD) and the second extend-add phase leaves the front's
+    // contribution-block columns out (plan_build.hip); where it stays with the four-wave kernel nothing changes.
+    bool fuse_ea = false ;
+    std::map<int, i64> carrier ;            // front -> a_off of its carrier among the regions collected for the next flush
 
     DenseScheduler (const std::vector<FrontD> &fr_, const i32 *ids_, int nf_, Schedule &S_, int flags_, const i32 *owner_,
         const i32 *grp0_, const i32 *grpn_, int rank_, int world_, const char *assign_cb_, const i64 *win_, const i32 *child_,
-        bool allow_half_, const HeadInfo *heads_)
+        bool allow_half_, const HeadInfo *heads_, const i64 *crel_, const std::vector<i64> *Ls_)
         : fr (fr_), ids (ids_), nf (nf_), S (S_), flags (flags_), owner (owner_), grp0 (grp0_), grpn (grpn_), rank (rank_),
-          world (world_), assign_cb (assign_cb_), win (win_), child (child_), allow_half (allow_half_), heads (heads_)
+          world (world_), assign_cb (assign_cb_), win (win_), child (child_), allow_half (allow_half_), heads (heads_), crel (crel_), Ls (Ls_)
     {
         cx = (flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;
         twin = (flags & CHOLMOD_HIP_PHI_TWIN) != 0 || cx ;
@@ -110,6 +121,8 @@ struct DenseScheduler
         xla = !(flags & CHOLMOD_HIP_NO_EXCHANGE_LOOKAHEAD) ;
         balance_cb = !use_big && !getenv ("CHOLMOD_HIP_NO_CB_BALANCE") ;
         early.assign (nf, -1) ; early_open.assign (nf, -1) ; pf_done.assign (nf, -1) ;
+        fuse_ea = (flags & CHOLMOD_HIP_FUSED_CB_EA) && world == 1 && allow_half && !twin && !use_big && w_min_tiles > 0
+            && assign_cb && child && crel && Ls ;
         choose_chain () ;
     }
 
@@ -385,6 +398,8 @@ struct DenseScheduler
             L.ng = (int) (S.gg.size () - L.goff) ;
             L.grid = (int) tiles ;
             L.half = (kind == K_UPD_W && tiles < w_half_max) ? 1 : 0 ;
+            L.fused = (kind == K_UPD_W && S.gfz.size () > L.goff
+                && std::any_of (S.gfz.begin () + L.goff, S.gfz.end (), [] (i32 z) { return z >= 0 ; })) ? 1 : 0 ;
             if (L.ng) S.launches.push_back (L) ;
             L = Launch {L.kind, 0, 0, S.gg.size (), 0, 0} ;
             tiles = 0 ;
@@ -406,10 +421,37 @@ struct DenseScheduler
             L.flops += 2.0 * elems * G.k * share ;
             L.aux = std::max (L.aux, (int) G.k) ;
             L.bytes += ((G.assign ? 8.0 : 16.0) * elems + 8.0 * ((double) G.m + G.n) * G.k) * share ;
+            if (kind == K_UPD_W && G.c_in_cb && !carrier.empty ())
+            {
+                auto it = carrier.find (G.front) ;
+                if (it != carrier.end () && it->second == G.a_off) L.bytes += carry_children (G) ;
+            }
             S.gg.push_back (G) ;
         }
         close_launch () ;
         v.clear () ;
+    }
+    // Region G -- about to become S.gg [S.gg.size ()] -- is the carrier of its front: the FuseD that goes with it, one
+    // inverse map per child.  Returns the bytes the children add to the launch: their entries that land in the
+    // contribution block, read once, and the maps.
+    double carry_children (const GemmGroup &G)
+    {
+        const FrontD &f = fr [G.front] ;
+        S.gfz.resize (S.gg.size (), -1) ;
+        S.gfz.push_back ((i32) S.fz.size ()) ;
+        S.fz.push_back (FuseD {S.invsize, G.front, f.child_begin, f.child_end - f.child_begin, f.ncb}) ;
+        double bytes = 0 ;
+        for (int c = f.child_begin ; c < f.child_end ; c++)
+        {
+            const FrontD &d = fr [child [c]] ;
+            // the child's rows are sorted: those past the parent's last column land in its contribution block
+            const i64 *r0 = Ls->data () + d.psi + d.nscol, *r1 = r0 + d.ncb ;
+            const int mcb = (int) (r1 - std::lower_bound (r0, r1, (i64) f.k1 + f.nscol)) ;
+            S.ivp.push_back (InvPair {crel [c], S.invsize, d.ncb, f.nscol, f.ncb, G.front, child [c], mcb}) ;
+            S.invsize += f.ncb ;
+            bytes += 8.0 * ((double) mcb * (mcb + 1) / 2) + 4.0 * f.ncb ;
+        }
+        return bytes ;
     }
     void flush_updates ()
     {
@@ -437,6 +479,7 @@ struct DenseScheduler
         flush_kind (pfv, K_UPD_PF) ;
         flush_kind (wav, K_UPD_W) ;
         flush_gathered () ;
+        carrier.clear () ;
     }
     // The update that closes the head [0, H) of front q -- everything to its right, contribution block included -- over the
     // rows the head reaches only: an entry of another row is a sum of products with exact zeros.  Two regions on row maps
@@ -735,6 +778,9 @@ struct DenseScheduler
             {
                 size_t nsm = small.size () ;
                 add_update (f, fid, f.nscol, x.kc, x.kk, f.ncb, f.ncb, true, x.wide) ;
+                if (fuse_ea && small.size () > nsm && x.kc == head_of (fid) && assign_cb [fid] && f.child_end > f.child_begin
+                    && !is_shared (fid) && !windowed (fid))
+                    carrier [fid] = small.back ().a_off ;
                 if (windowed (fid) && f.own_g > 1 && balance_cb && small.size () > nsm) balance_cb_tiles (x) ;
             }
         }
@@ -999,9 +1045,10 @@ struct DenseScheduler
 
 void schedule_dense (const std::vector<FrontD> &fr, const i32 *ids, int nf,
     Schedule &S, int flags, const i32 *owner, const i32 *grp0, const i32 *grpn, int rank, int world,
-    const char *assign_cb, const i64 *win, const i32 *child, bool allow_half, const HeadInfo *heads)
+    const char *assign_cb, const i64 *win, const i32 *child, bool allow_half, const HeadInfo *heads,
+    const i64 *crel, const std::vector<i64> *Ls)
 {
-    DenseScheduler D (fr, ids, nf, S, flags, owner, grp0, grpn, rank, world, assign_cb, win, child, allow_half, heads) ;
+    DenseScheduler D (fr, ids, nf, S, flags, owner, grp0, grpn, rank, world, assign_cb, win, child, allow_half, heads, crel, Ls) ;
     D.run () ;
 }
 

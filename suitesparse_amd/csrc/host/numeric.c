@@ -118,6 +118,17 @@ static int plan_flags_of (const cholmod_factor *L, const cholmod_common *Common)
     return flags ;
 }
 
+/* ... and what the host layer adds to them for the engine on its own account (not part of what L->hip_plan_ahead records of
+ * the caller's Common->hip_flags).  Ordinary real factorizations on one GPU: the contribution-block half of the extend-add
+ * rides with the update that first writes the block (cholmod_hip.h: CHOLMOD_HIP_FUSED_CB_EA); CHOLMOD_HIP_NO_FUSED_CB_EA=1
+ * in the environment, read when the plan is built, keeps the two-phase extend-add everywhere */
+static int engine_flags_of (const cholmod_factor *L, const cholmod_common *Common)
+{
+    const char *e = getenv ("CHOLMOD_HIP_NO_FUSED_CB_EA") ;
+    if (L->hip_is_twin || Common->hip_world > 1 || (e && atoi (e) != 0)) return 0 ;
+    return CHOLMOD_HIP_FUSED_CB_EA ;
+}
+
 static int ensure_plan_with (cholmod_factor *L, cholmod_common *Common, const int64_t *reach_p, const int32_t *reach_first) ;
 int ssamd_ensure_plan (cholmod_factor *L, cholmod_common *Common) { return ensure_plan_with (L, Common, NULL, NULL) ; }
 
@@ -138,10 +149,10 @@ static int ensure_plan_with (cholmod_factor *L, cholmod_common *Common, const in
     if (L->hip_plan) return TRUE ;
     const double t_plan = omp_get_wtime () ;
     cholmod_hip_plan *P = (reach_p && world == 1)
-        ? cholmod_hip_plan_create_reach ((int64_t) L->n, (int64_t) L->nsuper, L->super, L->pi, L->px, L->s, flags,
-            reach_p, reach_first, &st)
+        ? cholmod_hip_plan_create_reach ((int64_t) L->n, (int64_t) L->nsuper, L->super, L->pi, L->px, L->s,
+            flags | engine_flags_of (L, Common), reach_p, reach_first, &st)
         : cholmod_hip_plan_create_dist ((int64_t) L->n, (int64_t) L->nsuper,
-            L->super, L->pi, L->px, L->s, flags, world > 1 ? Common->hip_rank : 0, world, &st) ;
+            L->super, L->pi, L->px, L->s, flags | engine_flags_of (L, Common), world > 1 ? Common->hip_rank : 0, world, &st) ;
     Common->hip_plan_seconds = omp_get_wtime () - t_plan ;
     if (!P) return map_hip_status (st ? st : CHOLMOD_HIP_GPU_PROBLEM, Common, "HIP plan creation failed") ;
     /* (several ranks need an exchange: the Common->hip_allreduce callback, or the
