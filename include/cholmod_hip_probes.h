@@ -12,7 +12,10 @@ extern "C" {
 
 /* Dense fp64 C -= A*B' micro-benchmark on the engine's update kernel k_update2 (used by
  * bench.py to print the measured MFMA rate next to the 78.6 TFLOP/s spec).
- * Returns achieved flop/s, or a negative CHOLMOD_HIP_* code. */
+ * Returns achieved flop/s, or a negative CHOLMOD_HIP_* code.
+ * flags for the one-wave kernel k_update3: 8192 / 16384 / 32768 = 3 / 2 / 4 operand sets in flight, 524288 = two
+ * waves per tile, 1048576 = four tiles per workgroup (CHOLMOD_HIP_INVALID together with 524288), 262144 = 16 x 16
+ * super-tiles; cholmod_hip_debug_update_diff takes the same. */
 double cholmod_hip_bench_update_kernel (int64_t m, int64_t n, int64_t k,
     int iters, int flags) ;
 /* the outer update of a top front, trapezoid + square, as one launch or as two (tools/upd3.py pair) */

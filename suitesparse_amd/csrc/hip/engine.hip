@@ -2,11 +2,9 @@
 // (plan_build.hip / schedule_dense.hip derive it), the runner of its launch list, and the extern "C" shim declared in
 // include/cholmod_hip.h (the exchange between ranks and the gather: exchange.hip; the triangular solves: solve.hip).
 // One process drives one GPU.
-#include "kernels.hip.h"
+#include "update_launch.hip.h"
 #include "exchange_internal.hip.h"
 #include <thread>
-
-#define COMMA ,
 
 namespace {
 
@@ -229,9 +227,7 @@ static int run_launch (cholmod_hip_plan *P, const Launch &L, bool serial)
     const bool twin = !cx && (P->flags & CHOLMOD_HIP_PHI_TWIN) != 0 ;      // update kernels contract over the even columns
 // K<true> for a complex factor in its own storage, K<false> otherwise
 #define CX_LAUNCH(K, ...) do { if (cx) hipLaunchKernelGGL (K<true>, __VA_ARGS__) ; else hipLaunchKernelGGL (K<false>, __VA_ARGS__) ; } while (0)
-// the update kernels: 0 real, 1 twin (even-column contraction), 2 complex storage
-#define TW_LAUNCH(KA, KB, ...) do { if (cx) hipLaunchKernelGGL ((KA 2 KB), __VA_ARGS__) ; else if (twin) hipLaunchKernelGGL ((KA 1 KB), __VA_ARGS__) ; \
-                                    else hipLaunchKernelGGL ((KA 0 KB), __VA_ARGS__) ; } while (0)
+    const int tw = cx ? 2 : twin ? 1 : 0 ;                          // the update kernels' TW (update_launch.hip.h: with_tw)
     // (test hook CHOLMOD_HIP_TEST_DROP_WAITS=1: the cross-stream waits of the schedule are skipped -- the mutation the jitter
     // test must catch, tests/test_gpu_scale.py::test_stream_jitter_catches_a_dropped_wait; =2: only the joins with the far-row
     // gathers of the shared fronts, tests/test_dist.py)
@@ -262,22 +258,14 @@ static int run_launch (cholmod_hip_plan *P, const Launch &L, bool serial)
             {
                 // tuning: per-phase shader cycles of one front per launch (CHOLMOD_HIP_THIN_TIMING)
                 long long *tim = P->d_thin_tim ? P->d_thin_tim + 10 * (size_t) (&L - P->sch.launches.data ()) : nullptr ;
-#define THIN_LAUNCH(NW_, TIMED_, MINW_) \
-                hipLaunchKernelGGL ((k_thin_front<NW_, TIMED_, MINW_>), dim3 (L.grid), dim3 (64 * NW_), thin_front_lds_bytes (L.aux), st, \
+// (CX_: a complex factor in its own storage; it is never timed)
+#define THIN_LAUNCH(NW_, TIMED_, MINW_, CX_) \
+                hipLaunchKernelGGL ((k_thin_front<NW_, TIMED_, MINW_, CX_>), dim3 (L.grid), dim3 (64 * NW_), thin_front_lds_bytes (L.aux), st, \
                     P->d_sm + L.goff, P->d_smd + L.goff, P->d_sp01 + 2 * L.goff, P->d_cdesc, P->d_relmap, P->d_Ls, P->d_Sp, \
                     P->s_unpacked ? P->d_Snz : nullptr, P->d_Si, P->d_Sx, P->cur_beta, \
-                    P->d_Lx, P->d_cb, P->d_info, L.aux, P->d_amap, P->cur_mapped, tim)
-                if (cx)
-                {
-                    // complex storage: one wave per front up to 64 twin rows, four above
-#define THIN_LAUNCH_CX(NW_, MINW_) \
-                    hipLaunchKernelGGL ((k_thin_front<NW_, false, MINW_, true>), dim3 (L.grid), dim3 (64 * NW_), thin_front_lds_bytes (L.aux), st, \
-                        P->d_sm + L.goff, P->d_smd + L.goff, P->d_sp01 + 2 * L.goff, P->d_cdesc, P->d_relmap, P->d_Ls, P->d_Sp, \
-                        P->s_unpacked ? P->d_Snz : nullptr, P->d_Si, P->d_Sx, P->cur_beta, \
-                        P->d_Lx, P->d_cb, P->d_info, L.aux, P->d_amap, P->cur_mapped, (long long *) nullptr)
-                    if (L.aux > 64) THIN_LAUNCH_CX (4, 2) ; else THIN_LAUNCH_CX (1, 4) ;
-#undef THIN_LAUNCH_CX
-                }
+                    P->d_Lx, P->d_cb, P->d_info, L.aux, P->d_amap, P->cur_mapped, (TIMED_) ? tim : (long long *) nullptr)
+                // complex storage: one wave per front up to 64 twin rows, four above
+                if (cx) { if (L.aux > 64) THIN_LAUNCH (4, false, 2, true) ; else THIN_LAUNCH (1, false, 4, true) ; }
                 else if (L.leaf_pw && P->cur_mapped && !P->s_unpacked && !tim)
                 {
                     // leaf fronts two to a wave, once the assembly map of the resident S exists
@@ -292,16 +280,16 @@ static int run_launch (cholmod_hip_plan *P, const Launch &L, bool serial)
 #undef LEAF_PW
 #undef LEAF_LAUNCH
                 }
-                else if (tim) { if (L.aux <= 64) THIN_LAUNCH (1, true, 4) ; else THIN_LAUNCH (4, true, 2) ; }
-                else if (L.aux > 64) THIN_LAUNCH (4, false, 2) ;
+                else if (tim) { if (L.aux <= 64) THIN_LAUNCH (1, true, 4, false) ; else THIN_LAUNCH (4, true, 2, false) ; }
+                else if (L.aux > 64) THIN_LAUNCH (4, false, 2, false) ;
                 else
                 {
                     // one wave per front: the register budget (waves per SIMD the compiler must
                     // allow) by size class -- the LDS of the wider classes caps the occupancy
                     // anyway (9.6 / 16.9 KB per front), and 80 registers spill
                     const int w = thin_minw (L.aux <= 32 ? 0 : L.aux <= 48 ? 1 : 2) ;
-                    if (w == 3) THIN_LAUNCH (1, false, 3) ;
-                    else THIN_LAUNCH (1, false, 4) ;
+                    if (w == 3) THIN_LAUNCH (1, false, 3, false) ;
+                    else THIN_LAUNCH (1, false, 4, false) ;
                 }
 #undef THIN_LAUNCH
             }
@@ -347,8 +335,11 @@ static int run_launch (cholmod_hip_plan *P, const Launch &L, bool serial)
                 P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
             break ;
         case K_UPD_SMALL:
-            TW_LAUNCH (k_update2<SMALL COMMA SMALL COMMA BKK COMMA 2 COMMA false COMMA, >, dim3 (L.grid), dim3 (256), 0, st,
-                P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
+            with_tw (tw, [&] (auto TW)
+            {
+                hipLaunchKernelGGL ((k_update2<SMALL, SMALL, BKK, 2, false, decltype (TW)::value>), dim3 (L.grid), dim3 (256), 0, st,
+                    P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
+            }) ;
             break ;
         case K_DIAG:
             hipLaunchKernelGGL (k_diag<false>, dim3 (L.grid), dim3 (256), 0, st, P->d_dg + L.goff, P->d_Lx, P->d_info, P->d_dinv, (long long *) nullptr) ;
@@ -359,50 +350,28 @@ static int run_launch (cholmod_hip_plan *P, const Launch &L, bool serial)
                 P->d_rg + L.goff, L.ng, P->d_Lx, P->d_info, P->d_dinv) ;
             break ;
         case K_UPD_W:
-            // operand sets in flight: four for long contractions, two for short ones (tools/upd3.py)
-            if (P->upd3_wg4)
             {
-                // (several ranks) four tiles per workgroup: see k_update3
-                const unsigned g4 = (unsigned) (((L.grid + 31) / 32) * 8) ;
-                if (L.aux >= 1024) TW_LAUNCH (k_update3<4 COMMA, COMMA 4>, dim3 (g4), dim3 (256), 0, st, P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
-                else TW_LAUNCH (k_update3<2 COMMA, COMMA 4>, dim3 (g4), dim3 (256), 0, st, P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
+                // (a fused launch: a region takes its children's contribution-block entries with it, k_update3f)
+                const Upd3Fuse fz {P->d_gfz ? P->d_gfz + L.goff : nullptr, P->d_fz, P->d_cdesc, P->d_invmap} ;
+                const int rl = launch_update3 (st, P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb,
+                    Upd3Shape {L.grid, L.aux, L.half != 0, P->upd3_wg4, tw}, L.fused ? &fz : nullptr) ;
+                if (rl != CHOLMOD_HIP_OK) return rl ;
             }
-            else if (L.fused)
-            {
-                // a region of the launch takes its children's contribution-block entries with it (k_update3f; one GPU, real)
-                if (!P->d_fz || cx || twin) { fprintf (stderr, "cholmod_hip: a fused update launch without its side arrays\n") ; return CHOLMOD_HIP_INVALID ; }
-                const unsigned gh = 2u * (unsigned) ((L.grid + 7) / 8 * 8) ;
-#define UPD3F_ARGS P->d_gg + L.goff, L.ng, P->d_gfz + L.goff, P->d_fz, P->d_cdesc, P->d_invmap, P->d_Lx, P->d_cb
-                if (L.half && L.aux >= 1024) hipLaunchKernelGGL ((k_update3f<4, true>), dim3 (gh), dim3 (64), 0, st, UPD3F_ARGS) ;
-                else if (L.half) hipLaunchKernelGGL ((k_update3f<2, true>), dim3 (gh), dim3 (64), 0, st, UPD3F_ARGS) ;
-                else if (L.aux >= 1024) hipLaunchKernelGGL ((k_update3f<4, false>), dim3 (L.grid), dim3 (64), 0, st, UPD3F_ARGS) ;
-                else hipLaunchKernelGGL ((k_update3f<2, false>), dim3 (L.grid), dim3 (64), 0, st, UPD3F_ARGS) ;
-#undef UPD3F_ARGS
-            }
-            else if (L.half)
-            {
-                // two waves per tile (k_update3 <..., HALF>): the launches of 512 .. 10 240 tiles, schedule_dense.hip
-                const unsigned gh = 2u * (unsigned) ((L.grid + 7) / 8 * 8) ;
-                if (L.aux >= 1024) TW_LAUNCH (k_update3<4 COMMA, COMMA 1 COMMA true>, dim3 (gh), dim3 (64), 0, st, P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
-                else TW_LAUNCH (k_update3<2 COMMA, COMMA 1 COMMA true>, dim3 (gh), dim3 (64), 0, st, P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
-            }
-            else if (L.aux >= 1024) TW_LAUNCH (k_update3<4 COMMA, >, dim3 (L.grid), dim3 (64), 0, st, P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
-            else TW_LAUNCH (k_update3<2 COMMA, >, dim3 (L.grid), dim3 (64), 0, st, P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb) ;
             break ;
         case K_UPD_G:
             // head updates over the rows their heads reach (schedule_dense.hip: add_head_gathered), sized as K_UPD_W
-            if (L.half)
             {
-                const unsigned gh = 2u * (unsigned) ((L.grid + 7) / 8 * 8) ;
-                if (L.aux >= 1024) hipLaunchKernelGGL ((k_update3g<4, true>), dim3 (gh), dim3 (64), 0, st, P->d_xg + L.goff, L.ng, P->d_gmap, P->d_Lx, P->d_cb) ;
-                else hipLaunchKernelGGL ((k_update3g<2, true>), dim3 (gh), dim3 (64), 0, st, P->d_xg + L.goff, L.ng, P->d_gmap, P->d_Lx, P->d_cb) ;
+                const int rl = launch_update3g (st, P->d_xg + L.goff, L.ng, P->d_gmap, P->d_Lx, P->d_cb,
+                    Upd3Shape {L.grid, L.aux, L.half != 0, P->upd3_wg4, tw}) ;
+                if (rl != CHOLMOD_HIP_OK) return rl ;
             }
-            else if (L.aux >= 1024) hipLaunchKernelGGL ((k_update3g<4, false>), dim3 (L.grid), dim3 (64), 0, st, P->d_xg + L.goff, L.ng, P->d_gmap, P->d_Lx, P->d_cb) ;
-            else hipLaunchKernelGGL ((k_update3g<2, false>), dim3 (L.grid), dim3 (64), 0, st, P->d_xg + L.goff, L.ng, P->d_gmap, P->d_Lx, P->d_cb) ;
             break ;
         case K_UPD_PF:
-            TW_LAUNCH (k_update2f<, >, dim3 (L.grid), dim3 (256), 0, st,
-                P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb, P->d_info) ;
+            with_tw (tw, [&] (auto TW)
+            {
+                hipLaunchKernelGGL ((k_update2f<decltype (TW)::value>), dim3 (L.grid), dim3 (256), 0, st,
+                    P->d_gg + L.goff, L.ng, P->d_Lx, P->d_cb, P->d_info) ;
+            }) ;
             break ;
     }
     if (!serial && L.rec_ev >= 0) HIPCHK (hipEventRecord (P->sync_ev [L.rec_ev], st)) ;

@@ -2157,29 +2157,39 @@ __device__ __forceinline__ void update_tile_w (const GemmGroup &G, int I, int J,
 // HALF (round 5; one tile per workgroup only): blocks b and b + 8 -- the same XCD, hence the same tile walk -- take the left and
 // the right 32 columns of tile ((b >> 4) << 3) | (b & 7) of the one-wave launch; the grid is twice that launch's, rounded up
 // to whole groups of eight.
-template <int DEPTH, int TW = 0, int WPB = 1, bool HALF = false>
-__global__ void __launch_bounds__(64 * WPB, 2) k_update3 (const GemmGroup *g, int ng, double *Lx, double *CB)
+template <int WPB, bool HALF>
+__device__ __forceinline__ int upd3_virtual_block (int &cofs)
 {
     int vb = (int) blockIdx.x ;
-    int cofs = 0 ;
+    cofs = 0 ;
     if constexpr (WPB > 1) vb = ((vb >> 3) * WPB + (int) (threadIdx.x >> 6)) * 8 + (vb & 7) ;
     if constexpr (HALF) { cofs = ((vb >> 3) & 1) * 32 ; vb = ((vb >> 4) << 3) | (vb & 7) ; }
-    int gi = find_group (g, ng, vb, &GemmGroup::tile_start) ;
-    GemmGroup G = g [gi] ;
+    return vb ;
+}
+
+// The tile (or the half at column cofs of the tile) that virtual block vb of the launch owns in region G, if any: a whole
+// one runs without the edge masks.  The one entry of k_update3 / k_update3f / k_update3g into update_tile_w.
+template <int DEPTH, int TW, bool HALF, bool GATHER = false, bool FUSE = false>
+__device__ __forceinline__ void upd3_run_tile (const GemmGroup &G, int vb, int cofs, double *Lx, double *CB,
+    const i32 *rmap = nullptr, const FuseD *fz = nullptr, const ChildD *cdesc = nullptr, const i32 *invmap = nullptr)
+{
+    constexpr int NQ = HALF ? 1 : 2 ;
     int I, J ;
     if (vb - G.tile_start >= G.nblk) return ;
     if (!decode_tile (G, vb - G.tile_start, I, J)) return ;
-    if constexpr (HALF)
-    {
-        if (G.n - J * 64 - cofs <= 0) return ;                          // (the last tile column is at most 32 wide)
-        if (G.m - I * 64 >= 64 && G.n - J * 64 - cofs >= 32) update_tile_w<DEPTH, false, TW, 1> (G, I, J, Lx, CB, cofs) ;
-        else update_tile_w<DEPTH, true, TW, 1> (G, I, J, Lx, CB, cofs) ;
-    }
-    else
-    {
-        if (G.m - I * 64 >= 64 && G.n - J * 64 >= 64) update_tile_w<DEPTH, false, TW> (G, I, J, Lx, CB) ;
-        else update_tile_w<DEPTH, true, TW> (G, I, J, Lx, CB) ;
-    }
+    if constexpr (!HALF) cofs = 0 ;                                     // (a whole tile: known to the compiler)
+    if (HALF && G.n - J * 64 - cofs <= 0) return ;                      // (the last tile column is at most 32 wide)
+    if (G.m - I * 64 >= 64 && G.n - J * 64 - cofs >= 32 * NQ) update_tile_w<DEPTH, false, TW, NQ, GATHER, FUSE> (G, I, J, Lx, CB, cofs, rmap, fz, cdesc, invmap) ;
+    else update_tile_w<DEPTH, true, TW, NQ, GATHER, FUSE> (G, I, J, Lx, CB, cofs, rmap, fz, cdesc, invmap) ;
+}
+
+template <int DEPTH, int TW = 0, int WPB = 1, bool HALF = false>
+__global__ void __launch_bounds__(64 * WPB, 2) k_update3 (const GemmGroup *g, int ng, double *Lx, double *CB)
+{
+    int cofs ;
+    const int vb = upd3_virtual_block<WPB, HALF> (cofs) ;
+    const GemmGroup G = g [find_group (g, ng, vb, &GemmGroup::tile_start)] ;
+    upd3_run_tile<DEPTH, TW, HALF> (G, vb, cofs, Lx, CB) ;
 }
 
 // k_update3 for a launch that holds a carrier (update_tile_w: FUSE): gfz [q] = the FuseD of region q of the launch, -1: the
@@ -2188,27 +2198,12 @@ template <int DEPTH, bool HALF = false>
 __global__ void __launch_bounds__(64, 2) k_update3f (const GemmGroup *g, int ng, const i32 *gfz, const FuseD *fzs, const ChildD *cdesc,
     const i32 *invmap, double *Lx, double *CB)
 {
-    int vb = (int) blockIdx.x ;
-    int cofs = 0 ;
-    if constexpr (HALF) { cofs = ((vb >> 3) & 1) * 32 ; vb = ((vb >> 4) << 3) | (vb & 7) ; }
+    int cofs ;
+    const int vb = upd3_virtual_block<1, HALF> (cofs) ;
     const int gi = find_group (g, ng, vb, &GemmGroup::tile_start) ;
-    GemmGroup G = g [gi] ;
+    const GemmGroup G = g [gi] ;
     const int z = gfz [gi] ;
-    const FuseD *fz = z >= 0 ? fzs + z : nullptr ;
-    int I, J ;
-    if (vb - G.tile_start >= G.nblk) return ;
-    if (!decode_tile (G, vb - G.tile_start, I, J)) return ;
-    if constexpr (HALF)
-    {
-        if (G.n - J * 64 - cofs <= 0) return ;
-        if (G.m - I * 64 >= 64 && G.n - J * 64 - cofs >= 32) update_tile_w<DEPTH, false, 0, 1, false, true> (G, I, J, Lx, CB, cofs, nullptr, fz, cdesc, invmap) ;
-        else update_tile_w<DEPTH, true, 0, 1, false, true> (G, I, J, Lx, CB, cofs, nullptr, fz, cdesc, invmap) ;
-    }
-    else
-    {
-        if (G.m - I * 64 >= 64 && G.n - J * 64 >= 64) update_tile_w<DEPTH, false, 0, 2, false, true> (G, I, J, Lx, CB, 0, nullptr, fz, cdesc, invmap) ;
-        else update_tile_w<DEPTH, true, 0, 2, false, true> (G, I, J, Lx, CB, 0, nullptr, fz, cdesc, invmap) ;
-    }
+    upd3_run_tile<DEPTH, 0, HALF, false, true> (G, vb, cofs, Lx, CB, nullptr, z >= 0 ? fzs + z : nullptr, cdesc, invmap) ;
 }
 
 // The head update of a front restricted to the rows the head reaches (GatherGroup; schedule_dense.hip): k_update3 on the
@@ -2216,26 +2211,11 @@ __global__ void __launch_bounds__(64, 2) k_update3f (const GemmGroup *g, int ng,
 template <int DEPTH, bool HALF = false>
 __global__ void __launch_bounds__(64, 2) k_update3g (const GatherGroup *g, int ng, const i32 *rmap, double *Lx, double *CB)
 {
-    int vb = (int) blockIdx.x ;
-    int cofs = 0 ;
-    if constexpr (HALF) { cofs = ((vb >> 3) & 1) * 32 ; vb = ((vb >> 4) << 3) | (vb & 7) ; }
+    int cofs ;
+    const int vb = upd3_virtual_block<1, HALF> (cofs) ;
     const int gi = find_group (g, ng, vb, &GatherGroup::tile_start) ;
     const GemmGroup G = g [gi].g ;
-    const i32 *map = rmap + g [gi].map ;
-    int I, J ;
-    if (vb - G.tile_start >= G.nblk) return ;
-    if (!decode_tile (G, vb - G.tile_start, I, J)) return ;
-    if constexpr (HALF)
-    {
-        if (G.n - J * 64 - cofs <= 0) return ;
-        if (G.m - I * 64 >= 64 && G.n - J * 64 - cofs >= 32) update_tile_w<DEPTH, false, 0, 1, true> (G, I, J, Lx, CB, cofs, map) ;
-        else update_tile_w<DEPTH, true, 0, 1, true> (G, I, J, Lx, CB, cofs, map) ;
-    }
-    else
-    {
-        if (G.m - I * 64 >= 64 && G.n - J * 64 >= 64) update_tile_w<DEPTH, false, 0, 2, true> (G, I, J, Lx, CB, 0, map) ;
-        else update_tile_w<DEPTH, true, 0, 2, true> (G, I, J, Lx, CB, 0, map) ;
-    }
+    upd3_run_tile<DEPTH, 0, HALF, true> (G, vb, cofs, Lx, CB, rmap + g [gi].map) ;
 }
 
 // ---- trailing update that also factors the next diagonal block ------------------

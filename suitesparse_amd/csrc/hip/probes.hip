@@ -2,6 +2,8 @@
 // (tools/, bench.py's measured ceilings).  Built into lib/libcholmod_amd_probes.so,
 // NOT into the product library.
 #include "probe_kernels.hip.h"
+#define UPD3_PROBE_DEPTH3       // k_update3<3>: an instantiation of this library only (flag 8192; bench.py times it)
+#include "update_launch.hip.h"
 #include "../../../include/cholmod_hip.h"
 #include "../../../include/cholmod_hip_probes.h"
 
@@ -23,6 +25,15 @@ static int probe_device ()
     int cnt = 0 ;
     return (hipGetDeviceCount (&cnt) == hipSuccess && cnt > 0) ? 1 : 0 ;
 }
+// The one-wave update kernel a probe's `flags` select, as update_launch.hip.h takes it: 524288: half tiles (two waves per
+// 64 x 64 tile, 64 x 32 each), 1048576: four tiles per workgroup (not both); operand sets in flight 3 / 2 / 4 by 8192 / 16384 /
+// 32768, with none of them 3 for whole tiles, one per workgroup, and 2 otherwise.
+static Upd3Shape upd3_shape (const GemmGroup &G, int flags)
+{
+    const bool half = (flags & 524288) != 0, wg4 = (flags & 1048576) != 0 ;
+    const int depth = (flags & 8192) ? 3 : (flags & 16384) ? 2 : (flags & 32768) ? 4 : (half || wg4) ? 2 : 3 ;
+    return Upd3Shape {G.nblk, G.k, half, wg4, 0, depth} ;
+}
 static int raise_lds_limits ()
 {
     HIPCHK (hipFuncSetAttribute ((const void *) k_trsm_mfma<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)) ;
@@ -36,6 +47,7 @@ extern "C" {
 double cholmod_hip_bench_update_kernel (int64_t m, int64_t n, int64_t k, int iters, int flags)
 {
     if (m <= 0 || n <= 0 || k <= 0 || iters <= 0) return CHOLMOD_HIP_INVALID ;
+    if ((flags & 524288) && (flags & 1048576)) return CHOLMOD_HIP_INVALID ;      // (half tiles run one to a workgroup)
     if (!probe_device ()) return CHOLMOD_HIP_NO_DEVICE ;
     // A: m x k, B: n x k (both ld = max(m,n)), C: m x n, all in one "Lx" buffer
     // flag 131072: the layout of a real front -- an odd leading dimension and operand offsets that are
@@ -88,18 +100,8 @@ double cholmod_hip_bench_update_kernel (int64_t m, int64_t n, int64_t k, int ite
     (void) hipEventCreate (&e0) ; (void) hipEventCreate (&e1) ;
     auto launch = [&] ()
     {
-        if (flags & 524288)     // (round 5) half tiles: two waves per 64 x 64 tile, 64 x 32 each; depth 4 (flag 32768) or 2
-        {
-            const unsigned g2 = 2u * (unsigned) ((grid + 7) / 8 * 8) ;
-            if (flags & 32768) hipLaunchKernelGGL ((k_update3<4, 0, 1, true>), dim3 (g2), dim3 (64), 0, 0, dg, 1, d, d) ;
-            else hipLaunchKernelGGL ((k_update3<2, 0, 1, true>), dim3 (g2), dim3 (64), 0, 0, dg, 1, d, d) ;
-        }
-        else if (flags & 8192)       // third generation: one wave per tile, no LDS (operand sets in flight: 3 / 2 / 4)
-            hipLaunchKernelGGL ((k_update3<3>), dim3 (grid), dim3 (64), 0, 0, dg, 1, d, d) ;
-        else if (flags & 16384)
-            hipLaunchKernelGGL ((k_update3<2>), dim3 (grid), dim3 (64), 0, 0, dg, 1, d, d) ;
-        else if (flags & 32768)
-            hipLaunchKernelGGL ((k_update3<4>), dim3 (grid), dim3 (64), 0, 0, dg, 1, d, d) ;
+        if (flags & (8192 | 16384 | 32768 | 524288 | 1048576))      // third generation: one wave per tile, no LDS (upd3_shape)
+            (void) launch_update3 (0, dg, 1, d, d, upd3_shape (G, flags)) ;
         else if (flags & 1)      // the first-generation VALU kernel (cross-check)
             hipLaunchKernelGGL ((k_update<SMALL, SMALL, BKK, false>), dim3 (grid), dim3 (256), 0, 0, dg, 1, d, d) ;
         else if (small && (flags & 256))
@@ -179,10 +181,10 @@ double cholmod_hip_bench_update_pair (int64_t m1, int64_t n1, int64_t m2, int64_
     {
         if (mode == 1)
         {
-            hipLaunchKernelGGL ((k_update3<4>), dim3 (sep [0].nblk), dim3 (64), 0, 0, dg + 2, 1, d, d) ;
-            hipLaunchKernelGGL ((k_update3<4>), dim3 (sep [1].nblk), dim3 (64), 0, 0, dg + 3, 1, d, d) ;
+            (void) launch_update3 (0, dg + 2, 1, d, d, Upd3Shape {sep [0].nblk, (int) k, false, false, 0, 4}) ;
+            (void) launch_update3 (0, dg + 3, 1, d, d, Upd3Shape {sep [1].nblk, (int) k, false, false, 0, 4}) ;
         }
-        else hipLaunchKernelGGL ((k_update3<4>), dim3 (grid2), dim3 (64), 0, 0, dg, 2, d, d) ;
+        else (void) launch_update3 (0, dg, 2, d, d, Upd3Shape {grid2, (int) k, false, false, 0, 4}) ;
     } ;
     hipEvent_t e0, e1 ;
     (void) hipEventCreate (&e0) ; (void) hipEventCreate (&e1) ;
@@ -480,6 +482,7 @@ double cholmod_hip_bench_mfma_ceiling (int waves_per_simd, int nacc, int iters, 
 double cholmod_hip_debug_update_diff (int64_t m, int64_t n, int64_t k, int tri, int assign, int flags)
 {
     if (m <= 0 || n <= 0 || k <= 0 || (tri && m < n)) return CHOLMOD_HIP_INVALID ;
+    if ((flags & 524288) && (flags & 1048576)) return CHOLMOD_HIP_INVALID ;      // (half tiles run one to a workgroup)
     if (!probe_device ()) return CHOLMOD_HIP_NO_DEVICE ;
     i64 ld = std::max (m, n) + 3 ;
     i64 a_off = 1, b_off = 1 + ld * k, c_off = 2 + 2 * ld * k ;      // (odd offsets: 8-byte alignment only)
@@ -514,11 +517,7 @@ double cholmod_hip_debug_update_diff (int64_t m, int64_t n, int64_t k, int tri, 
             HIPCHK (hipMemcpy (dg, &G, sizeof (G), hipMemcpyHostToDevice)) ;
         }
         if (pass == 0) hipLaunchKernelGGL ((k_update2<SMALL, SMALL, BKK, 2, false>), dim3 (G.nblk), dim3 (256), 0, 0, dg, 1, d, d) ;
-        else if ((flags & 524288) && (flags & 32768)) hipLaunchKernelGGL ((k_update3<4, 0, 1, true>), dim3 (2 * ((G.nblk + 7) / 8 * 8)), dim3 (64), 0, 0, dg, 1, d, d) ;
-        else if (flags & 524288) hipLaunchKernelGGL ((k_update3<2, 0, 1, true>), dim3 (2 * ((G.nblk + 7) / 8 * 8)), dim3 (64), 0, 0, dg, 1, d, d) ;
-        else if (flags & 16384) hipLaunchKernelGGL ((k_update3<2>), dim3 (G.nblk), dim3 (64), 0, 0, dg, 1, d, d) ;
-        else if (flags & 32768) hipLaunchKernelGGL ((k_update3<4>), dim3 (G.nblk), dim3 (64), 0, 0, dg, 1, d, d) ;
-        else hipLaunchKernelGGL ((k_update3<3>), dim3 (G.nblk), dim3 (64), 0, 0, dg, 1, d, d) ;
+        else if (launch_update3 (0, dg, 1, d, d, upd3_shape (G, flags)) != CHOLMOD_HIP_OK) { (void) hipFree (d) ; (void) hipFree (dg) ; return CHOLMOD_HIP_INVALID ; }
         HIPCHK (hipDeviceSynchronize ()) ;
         HIPCHK (hipMemcpy ((pass ? r1 : r0).data (), d, total * sizeof (double), hipMemcpyDeviceToHost)) ;
     }
@@ -662,7 +661,7 @@ int cholmod_hip_probe_overlap (const uint32_t *mask_a, const uint32_t *mask_b, i
     HIPCHK (hipMemcpy (dg, &G, sizeof (G), hipMemcpyHostToDevice)) ;
     hipEvent_t a0, a1, b0, b1 ;
     (void) hipEventCreate (&a0) ; (void) hipEventCreate (&a1) ; (void) hipEventCreate (&b0) ; (void) hipEventCreate (&b1) ;
-    auto upd = [&] () { hipLaunchKernelGGL ((k_update3<4>), dim3 (G.nblk), dim3 (64), 0, sa, dg, 1, d, d) ; } ;
+    auto upd = [&] () { (void) launch_update3 (sa, dg, 1, d, d, Upd3Shape {G.nblk, G.k, false, false, 0, 4}) ; } ;
     auto chain = [&] () { for (int q = 0 ; q < nchain ; q++) hipLaunchKernelGGL (k_where_am_i, dim3 (chain_blocks), dim3 (64), 0, sb, w, (long long) chain_us * 100) ; } ;
     float t = 0 ;
     upd () ; HIPCHK (hipDeviceSynchronize ()) ;

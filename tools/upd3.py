@@ -20,6 +20,7 @@ from suitesparse_amd import cholmod as ch
 
 pr = ch.probes()
 TRI, NOSWZ, ODD, D2, D3, D4, SWZ16 = 65536, 32, 131072, 16384, 8192, 32768, 262144
+HALF, WG4 = 524288, 1048576     # two waves per tile; four tiles per workgroup (not both)
 mode = sys.argv[1] if len(sys.argv) > 1 else "standalone"
 out = {}
 if mode == "standalone":
@@ -58,7 +59,6 @@ elif mode == "tail":
 elif mode == "half":
     # (round 5) half tiles -- two waves per 64 x 64 tile -- on the region sizes of the mid-size problems' top fronts:
     # agreement with k_update2 on ragged / triangular / assign regions, then rate against the whole-tile form and k_update2
-    HALF = 524288
     out = {"diff": {}, "TFLOPs": {}}
     for fl in (HALF | D2, HALF | D4):
         for (m, n, k, tri, asg) in ((64, 64, 64, 0, 0), (200, 130, 67, 0, 0), (333, 333, 129, 1, 0), (1000, 700, 512, 1, 1), (129, 65, 4, 0, 1),
