@@ -62,8 +62,8 @@ struct ZeroGroup { i64 off; i64 len; i32 blk_start; i32 pad; };
 struct PfGroup { i64 off; i32 lda; i32 nb; i32 front; i32 col0; };
 struct TrGroup { i64 l_off; i64 b_off; i32 lda; i32 m; i32 nb; i32 front;
                  i32 col0; i32 blk_start; };
-// the 256-column panel chain (k_diag / k_rowsolve): a diagonal sub-block of a front and the
-// rows below it
+// the 256-column panel chain (k_diag / k_rowsolve, chain256_kernels.hip.h): a diagonal sub-block of a
+// front and the rows below it
 struct DgGroup { i64 off; i32 lda; i32 w; i32 front; i32 col0; i32 slot; i32 pad; };
 struct RsGroup { i64 l_off; i64 b_off; i32 lda; i32 m; i32 w; i32 front; i32 col0; i32 blk_start; i32 slot; i32 pad; };
 struct GemmGroup {
@@ -146,7 +146,7 @@ struct XchgD {
 // k_win_move: one workgroup = one column x WIN_ROWS rows
 #define WIN_ROWS 8192
 struct WinD { i64 store ; i64 win ; i32 ld ; i32 c0, c1 ; i32 r0 ; i32 nrows ; i32 own_w, own_g, own_r ; i32 mode ; i32 blk_start ; } ;
-// the 256-column chain (k_diag / k_rowsolve / k_chainf)
+// the 256-column chain (k_diag / k_rowsolve / k_chainf, chain256_kernels.hip.h)
 #define DG_W 256
 #define RS_ROWS 64
 struct CfGroup { i64 l_off ; i32 lda ; i32 w ; i32 front ; i32 col0 ; i32 m1 ; i32 slot ; i32 fslot ; i32 dstart ; i32 bstart ; i32 off2 ; i32 m2 ; i32 off3 ; i32 m3 ; i32 pad ; } ;

@@ -3,6 +3,7 @@
 // include/cholmod_hip.h (the exchange between ranks and the gather: exchange.hip; the triangular solves: solve.hip).
 // One process drives one GPU.
 #include "update_launch.hip.h"
+#include "chain256_kernels.hip.h"
 #include "exchange_internal.hip.h"
 #include <thread>
 

@@ -4,6 +4,7 @@
 #include "probe_kernels.hip.h"
 #define UPD3_PROBE_DEPTH3       // k_update3<3>: an instantiation of this library only (flag 8192; bench.py times it)
 #include "update_launch.hip.h"
+#include "chain256_kernels.hip.h"
 #include "../../../include/cholmod_hip.h"
 #include "../../../include/cholmod_hip_probes.h"
 

@@ -5,7 +5,7 @@
 //   outer block columns (OB = 512 ... 4096 columns, by the front's row count) closed by one K = OB update of everything to
 //   their right, contribution block included; inside one, a chain of 64-column steps (dpotrf of the diagonal block, dtrsm of
 //   the rows below, fused with their neighbours where the step allows: k_update2f, k_trsm_upd) with recursive-doubling
-//   trailing updates -- or the 256-column chain (k_chainf; the default on fronts shared between ranks).
+//   trailing updates -- or the 256-column chain (k_chainf, chain256_kernels.hip.h; the default on fronts shared between ranks).
 //   Reference: the dpotrf / dtrsm per supernode of CHOLMOD/Supernodal/t_cholmod_super_numeric.c:864-867, :997-1002 and the
 //   dsyrk / dgemm updates of :682-717, regrouped.
 //
@@ -861,7 +861,7 @@ struct DenseScheduler
         fuse_trsm = fuse_potrf && !(flags & CHOLMOD_HIP_NO_FUSED_TRSM) ;
     }
 
-    // ---- the panel chain in 256-column sub-blocks (kernels.hip.h: k_chainf, or k_diag / k_rowsolve) -----------------------
+    // ---- the panel chain in 256-column sub-blocks (chain256_kernels.hip.h: k_chainf, or k_diag / k_rowsolve) --------------
     // Per sub-block [i0, b1) of a front: the diagonal sub-block is factored and every row below it solved -- in ONE launch
     // (k_chainf: the diagonal sub-block spread over up to four workgroups that hand their row block of L on through flags),
     // or by one workgroup (k_diag) and a solve launch (k_rowsolve; CHOLMOD_HIP_NO_CHAINF).  A front shared between ranks: the
