@@ -437,6 +437,26 @@ int cholmod_l_hip_selinv_device (cholmod_sparse *A, cholmod_factor *L, double *Z
  * (Z (s [pi [k] + i], super [k] + j), i >= j, at px [k] + i + j nsrow; zeros above the diagonal of the diagonal blocks), in
  * the factor's ordering.  Computes the inverse if it is stale and waits for it.  Refusals as above. */
 int cholmod_l_hip_selinv_to_host (cholmod_factor *L, double *Zx, cholmod_common *Common) ;
+/* What backpropagation through the device path needs (csrc/host/grad.c; suitesparse_amd/autograd.py ties them into
+ * torch.autograd.Functions).  cholmod_l_hip_values_grad_device: G_dev (nnz (A) doubles on the device, A's entry order)
+ * receives, for every entry (i, j) of A the factorization reads,
+ *     alpha sum_{r < nrhs} ( U [i, r] V [j, r] + [i != j] U [j, r] V [i, r] )
+ * and exact +0.0 at every other entry (the ignored triangle, where the selected inverse gives NaN).  U_dev, V_dev: n-by-nrhs,
+ * column-major, on the device, in A's ordering, read only; they may be the same array.  With X = (A + beta I)^-1 B,
+ * Lambda = (A + beta I)^-1 gX, U = Lambda, V = X and alpha = -1 this is the gradient of a scalar with respect to A's values
+ * through the solve; the gradient with respect to B is Lambda itself.  A gives the PATTERN only and is hashed against
+ * L->hip_apat_* exactly as cholmod_l_hip_selinv_device does; a mismatch touches no device state.  Perm is handed to the
+ * plan on first use, as cholmod_l_hip_solve_device does.  Ordered on `stream`; the same inputs give the same bits.
+ * cholmod_l_hip_logdet_device: out_dev [0] (one double on the device) = log det (A + beta I) = 2 sum log L_jj of the factor
+ * resident on the device, in stream order and with the same bits every time; its gradient with respect to A's values is
+ * the selected inverse, once on the diagonal and twice off it.
+ * Both return FALSE with CHOLMOD_INVALID for NULL pointers, an unpacked A, an A with stype == 0, mismatched dimensions, a
+ * leading dimension smaller than n, a symbolic L, the GPU switched off (no host fallback), several ranks, an L not
+ * factorized on the device or without the pattern record -- the log-determinant also for L->minor < n --, with
+ * CHOLMOD_NOT_INSTALLED for a complex or zomplex A or L: all before a device is touched. */
+int cholmod_l_hip_values_grad_device (cholmod_sparse *A, cholmod_factor *L, double alpha, const double *U_dev, size_t ldu,
+    const double *V_dev, size_t ldv, size_t nrhs, double *G_dev, void *stream, cholmod_common *Common) ;
+int cholmod_l_hip_logdet_device (cholmod_factor *L, double *out_dev, void *stream, cholmod_common *Common) ;
 /* cholmod_l_factorize for new VALUES of A that already live in device memory (a matrix assembled on the GPU: the step of a
  * Newton, time-stepping or interior-point loop), without a trip through the host.  A supplies the PATTERN only (p, i,
  * stype, packed; A->x is never read and may be NULL); Ax_dev is a device pointer to nnz (A) doubles in A's own entry

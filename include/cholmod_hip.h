@@ -419,6 +419,40 @@ int cholmod_hip_selinv_release (cholmod_hip_plan *plan) ;
  * scratch  [6] 1 if Zx is current  [7] reserved, zero */
 int cholmod_hip_selinv_info (cholmod_hip_plan *plan, double *out8) ;
 
+/* (This entry point and the next: csrc/hip/grad.hip.)
+ * The gradient with respect to the values of A, sampled on the pattern of the resident S.  dU, dV: n-by-nrhs, column-major,
+ * in device memory, read only (dU == dV is legal); with perm = 1 in the caller's ordering (cholmod_hip_set_perm first),
+ * with perm = 0 in the factor's.  dG: nvalues doubles in the order of the value map (the array
+ * cholmod_hip_factorize_values_device takes).  For the caller's value k that the resident S reads as entry (i, j)
+ *     G [k] = alpha sum_{r < nrhs} ( U [i, r] V [j, r] + [i != j] U [j, r] V [i, r] )
+ * -- with U = Lambda = (A + beta I)^-1 gX, V = X = (A + beta I)^-1 B and alpha = -1 the gradient of a scalar through the
+ * solve.  "Reads" is the rule of the factorization and of cholmod_hip_selinv_gather_device: on or below the diagonal of the
+ * permuted S, row < n, the last of equal neighbours; every other value has no influence on L and receives exact +0.0
+ * (where the gather of the selected inverse writes NaN).  All of dG [0 .. nvalues) is written.
+ * One owner per entry of G, a fixed summation order, no floating-point atomics: the same inputs give the same bits.  With
+ * SD_BLOCK_MIN_NRHS (8) right-hand sides or more U and V are packed through Perm into panels [n][16] and a group of 16
+ * lanes reads a row as one 128-byte line; with fewer they are read in place, right-hand sides in index order.  The two
+ * paths may differ by rounding.
+ * Ordered on `stream` exactly as cholmod_hip_solve_device is (not during capture).  The first call of either path
+ * allocates its workspace (events; two panels [n][16]); after that nothing is allocated and the host does not wait.
+ * Work is divided by entries of S; the column of an entry comes from an i32 column-of-entry array (4 bytes of HBM per
+ * entry of S) that the first call after a cholmod_hip_upload_matrix builds on the device, without a host wait.
+ * Needs a resident packed S with its value map, not a numeric factor.  CHOLMOD_HIP_INVALID, before any device call: a NULL
+ * plan or pointer, a host-only plan, several ranks, ld < n, nrhs < 0, nvalues other than the map's, no value map for the
+ * current resident S, a product map set (the caller's values are then not entries of S), perm without a stored
+ * permutation, the plans of complex factors (CHOLMOD_HIP_PHI_TWIN, CHOLMOD_HIP_CX_STORAGE).  nrhs == 0 is a success that
+ * zero-fills dG; n == 0 or nvalues == 0 touches nothing. */
+int cholmod_hip_values_grad_device (cholmod_hip_plan *plan, int perm, double alpha, const double *dU, int64_t ldu,
+    const double *dV, int64_t ldv, int64_t nrhs, double *dG, int64_t nvalues, void *stream) ;
+/* dOut [0] (device memory) = 2 sum_j log L_jj = log det (A + beta I) of the resident factor: one pass over the n diagonal
+ * entries, per-workgroup partial sums in a fixed tree, then one workgroup over the partials in index order -- no
+ * floating-point atomics, the same factor gives the same bits (cholmod_hip_factor_checks returns the half of it to the
+ * host, waits for the stream and is not reproducible).  Ordered on `stream` as above; the first call allocates the
+ * partials (n / 256 doubles), after that nothing is allocated and the host does not wait.  CHOLMOD_HIP_INVALID, before any
+ * device call: a NULL plan or pointer, a host-only plan, several ranks, no numeric factor on the device, a last
+ * factorization that was not positive definite, the plans of complex factors. */
+int cholmod_hip_logdet_device (cholmod_hip_plan *plan, double *dOut, void *stream) ;
+
 /* Parity hooks: copy derived integer maps back to the host.
  *  sparent  [nsuper]     supernodal etree (reference :1025)
  *  level    [nsuper]     height of s in that tree (leaves 0)

@@ -150,6 +150,7 @@ API_SYMBOLS = [
     "cholmod_l_hip_solve_device", "cholmod_l_hip_residual_device", "cholmod_l_hip_refine_device",
     "cholmod_l_hip_factorize_values_device", "cholmod_l_hip_aat_product_map",
     "cholmod_l_hip_selinv_device", "cholmod_l_hip_selinv_to_host",
+    "cholmod_l_hip_values_grad_device", "cholmod_l_hip_logdet_device",
 ]
 HIP_SYMBOLS = [
     "cholmod_hip_probe", "cholmod_hip_memorysize", "cholmod_hip_set_device", "cholmod_hip_device_count",
@@ -165,6 +166,7 @@ HIP_SYMBOLS = [
     "cholmod_hip_get_maps", "cholmod_hip_get_stats", "cholmod_hip_set_profiling",
     "cholmod_hip_selinv_device", "cholmod_hip_selinv_gather_device", "cholmod_hip_selinv_download",
     "cholmod_hip_selinv_release", "cholmod_hip_selinv_info",
+    "cholmod_hip_values_grad_device", "cholmod_hip_logdet_device",
     "cholmod_hip_dense_partial_factor", "cholmod_hip_factor_checks", "cholmod_hip_factor_checks_local", "cholmod_hip_get_launch_profile", "cholmod_hip_debug_thin_cycles", "cholmod_hip_debug_launch_regions",
     "cholmod_hip_debug_cb_extend_add", "cholmod_hip_debug_fused_pair",
     "cholmod_hip_rccl_unique_id", "cholmod_hip_rccl_attach", "cholmod_hip_rccl_detach",
@@ -311,6 +313,10 @@ def lib(hooks=None):
     sig("cholmod_hip_selinv_info", C.c_int, [vp, vp])
     sig("cholmod_l_hip_selinv_device", C.c_int, [sp, fc, vp, vp, vp, cm])
     sig("cholmod_l_hip_selinv_to_host", C.c_int, [fc, vp, cm])
+    sig("cholmod_hip_values_grad_device", C.c_int, [vp, C.c_int, dbl, vp, i64, vp, i64, i64, vp, i64, vp])
+    sig("cholmod_hip_logdet_device", C.c_int, [vp, vp, vp])
+    sig("cholmod_l_hip_values_grad_device", C.c_int, [sp, fc, dbl, vp, sz, vp, sz, sz, vp, vp, cm])
+    sig("cholmod_l_hip_logdet_device", C.c_int, [fc, vp, vp, cm])
     sig("cholmod_hip_get_maps", C.c_int, [vp, vp, vp, vp])
     sig("cholmod_hip_get_stats", C.c_int, [vp, vp])
     sig("cholmod_hip_set_profiling", C.c_int, [vp, C.c_int])
@@ -615,6 +621,44 @@ class Session:
         if not ok:
             raise RuntimeError(f"cholmod_l_hip_selinv_device failed, status {self.cm.status}")
         return Z, d
+
+    def values_grad_device(self, A, Lf, U, V, alpha=1.0, out=None):
+        """cholmod_l_hip_values_grad_device: alpha sum_r (U [i, r] V [j, r] + [i != j] U [j, r] V [i, r]) at every entry
+        (i, j) of A the factorization reads, exact +0.0 at every other entry; with U = A^-1 gX, V = X = A^-1 B and
+        alpha = -1 the gradient of a scalar with respect to A's values through the solve.  U, V: device tensors as for
+        `solve_device`, of one shape, in A's ordering (they may be the same tensor).  Returns a 1-D tensor of length
+        nnz (A) in A's entry order, or writes into `out`.  Enqueued on torch's current stream; the same inputs give the
+        same bits."""
+        import torch
+        n = int(Lf.contents.n)
+        ldu, nrhs = self._device_layout("values_grad_device: U", n, U)
+        ldv, _ = self._device_layout("values_grad_device: V", n, V, like=U)
+        a = A.contents
+        nz = int(_view(a.p, a.ncol + 1, C.c_int64, np.int64)[-1]) if a.p else 0
+        if out is None:
+            out = torch.empty(nz, dtype=torch.float64, device=U.device)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.device == U.device):
+            raise ValueError("values_grad_device: out must be a torch.float64 tensor on the device of U")
+        if out.dim() != 1 or out.shape[0] != nz or not out.is_contiguous():
+            raise ValueError(f"values_grad_device: out must be 1-D, contiguous and of length nnz (A) = {nz}")
+        stream = torch.cuda.current_stream(U.device).cuda_stream
+        ok = self.L.cholmod_l_hip_values_grad_device(A, Lf, float(alpha), U.data_ptr() or 1, ldu, V.data_ptr() or 1, ldv,
+                                                     nrhs, out.data_ptr() or 2, stream, C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_values_grad_device failed, status {self.cm.status}")
+        return out
+
+    def logdet_device(self, Lf):
+        """cholmod_l_hip_logdet_device: log det (A + beta I) = 2 sum log L_jj of the factor resident on the device, as a
+        0-dim torch.float64 device tensor.  Enqueued on torch's current stream, no host wait; the same factor gives the
+        same bits."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((), dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if not self.L.cholmod_l_hip_logdet_device(Lf, out.data_ptr(), stream, C.byref(self.cm)):
+            raise RuntimeError(f"cholmod_l_hip_logdet_device failed, status {self.cm.status}")
+        return out
 
     def selinv_host(self, Lf):
         """cholmod_l_hip_selinv_to_host: the selected inverse in the layout of L->x (FactorView.x), xsize doubles, in

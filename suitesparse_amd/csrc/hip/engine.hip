@@ -21,6 +21,7 @@ static void free_device (cholmod_hip_plan *P)
 {
     drop_product_map (P) ;
     selinv_free (P) ;
+    grad_free (P) ;
     for (hipEvent_t e : {P->fv_ev_in, P->fv_ev_out}) if (e) (void) hipEventDestroy (e) ;
     P->fv_ev_in = P->fv_ev_out = nullptr ;
     if (P->prog_dev) { (void) hipHostFree (P->prog_dev) ; P->prog_dev = nullptr ; }
@@ -941,6 +942,7 @@ int cholmod_hip_upload_matrix (cholmod_hip_plan *P, const int64_t *Sp, const int
     P->s_unpacked = (Snz != nullptr) ;
     P->amap_valid = false ;         // a new pattern may have come with the new values
     P->rs_index_valid = false ;     // ... and the transposed index of the residual goes with the old one
+    P->gr_index_valid = false ;     // ... and the column-of-entry array of the gradient
     P->si_valid = false ;           // ... and the selected inverse is that of the old matrix
     P->s_cur_nz = nz ;
     P->vsrc_nz = 0 ;                // ... and the value map of the previous one is void

@@ -397,6 +397,10 @@ struct cholmod_hip_plan {
     struct SelInv *si = nullptr ;
     bool si_valid = false ;
     int factor_state = 0 ;
+    // gradients and the log-determinant (grad.hip): two panels, the partial sums, the column of every entry of the
+    // resident S (built at the first call, void when S is uploaded anew) and the events live behind `gr`
+    struct Grad *gr = nullptr ;
+    bool gr_index_valid = false ;
     // progress of the running factorization, readable from another host thread (cholmod_hip_progress): the host side
     // counts what it has enqueued; with markers enabled the device writes, in stream order, the sequence number of the
     // exchange it has entered / left into pinned host memory (prog_dev [0] / [1])
@@ -418,6 +422,8 @@ static inline const FrontD *whole_fronts (cholmod_hip_plan *P) { return P->world
 
 // selinv.hip: everything the selected inverse holds of a plan (cholmod_hip_plan_destroy)
 void selinv_free (cholmod_hip_plan *P) ;
+// grad.hip: likewise
+void grad_free (cholmod_hip_plan *P) ;
 
 namespace sship {
 

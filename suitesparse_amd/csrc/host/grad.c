@@ -1,0 +1,87 @@
+/* grad.c -- what backpropagation through the device path needs, in the host layer (cholmod.h):
+ * cholmod_l_hip_values_grad_device samples alpha (U V' + V U') on the entries of A the factorization reads -- the gradient of
+ * a scalar with respect to A's values through a solve --, cholmod_l_hip_logdet_device leaves log det (A + beta I) of the
+ * resident factor in device memory.  Both run on the engine (cholmod_hip_values_grad_device, cholmod_hip_logdet_device,
+ * csrc/hip/grad.hip); there is no host fallback.  Every argument is checked before a device is touched. */
+#include "host_internal.h"
+
+static int gr_status (int rc, cholmod_common *Common, const char *what)
+{
+    switch (rc)
+    {
+        case CHOLMOD_HIP_OK: return TRUE ;
+        case CHOLMOD_HIP_OUT_OF_MEMORY: ERROR (CHOLMOD_OUT_OF_MEMORY, what) ; return FALSE ;
+        case CHOLMOD_HIP_INVALID: ERROR (CHOLMOD_INVALID, what) ; return FALSE ;
+        default: ERROR (CHOLMOD_GPU_PROBLEM, what) ; return FALSE ;
+    }
+}
+
+/* what both entry points ask of L; TRUE: L->hip_plan holds the matrix L was last factorized from on the device */
+static int gr_factor_ready (cholmod_factor *L, int posdef, cholmod_common *Common)
+{
+    if (L->xtype == CHOLMOD_COMPLEX || L->xtype == CHOLMOD_ZOMPLEX)
+    { ERROR (CHOLMOD_NOT_INSTALLED, "gradients of a complex factor are not supported") ; return FALSE ; }
+    if (L->xtype != CHOLMOD_REAL || !L->is_super)
+    { ERROR (CHOLMOD_INVALID, "L must be a numeric supernodal factor") ; return FALSE ; }
+    if (posdef && L->minor < L->n) { ERROR (CHOLMOD_INVALID, "L is not positive definite") ; return FALSE ; }
+    /* the operands live in device memory: no fallback, whatever Common->hip_cpu_fallback says */
+    if (ssamd_resolve_use_gpu (Common) != 1) { ERROR (CHOLMOD_INVALID, "device gradients need Common->useGPU") ; return FALSE ; }
+    if (Common->hip_world > 1) { ERROR (CHOLMOD_INVALID, "device gradients run on one rank only") ; return FALSE ; }
+    if (!L->hip_plan || !L->hip_on_device)
+    { ERROR (CHOLMOD_INVALID, "L was not factorized on the device") ; return FALSE ; }
+    return TRUE ;
+}
+
+int cholmod_l_hip_values_grad_device (cholmod_sparse *A, cholmod_factor *L, double alpha, const double *U_dev, size_t ldu,
+    const double *V_dev, size_t ldv, size_t nrhs, double *G_dev, void *stream, cholmod_common *Common)
+{
+    RETURN_IF_NULL_COMMON (FALSE) ;
+    RETURN_IF_NULL (A, FALSE) ;
+    RETURN_IF_NULL (L, FALSE) ;
+    RETURN_IF_NULL (U_dev, FALSE) ;
+    RETURN_IF_NULL (V_dev, FALSE) ;
+    RETURN_IF_NULL (G_dev, FALSE) ;
+    RETURN_IF_NULL (A->p, FALSE) ;
+    if (A->xtype == CHOLMOD_COMPLEX || A->xtype == CHOLMOD_ZOMPLEX)
+    { ERROR (CHOLMOD_NOT_INSTALLED, "gradients of a complex matrix are not supported") ; return FALSE ; }
+    if (L->xtype == CHOLMOD_COMPLEX || L->xtype == CHOLMOD_ZOMPLEX)
+    { ERROR (CHOLMOD_NOT_INSTALLED, "gradients of a complex factor are not supported") ; return FALSE ; }
+    if (A->xtype != CHOLMOD_REAL && A->xtype != CHOLMOD_PATTERN) { ERROR (CHOLMOD_INVALID, "invalid xtype") ; return FALSE ; }
+    /* (A*A' and column subsets: the caller's entries are then not the entries of the factorized matrix) */
+    if (A->stype == 0) { ERROR (CHOLMOD_INVALID, "the gradient needs a symmetric A (stype != 0)") ; return FALSE ; }
+    if (!A->packed) { ERROR (CHOLMOD_INVALID, "A must be packed") ; return FALSE ; }
+    if (A->nrow != L->n || A->nrow != A->ncol) { ERROR (CHOLMOD_INVALID, "A and L dimensions do not match") ; return FALSE ; }
+    if (ldu < L->n || ldv < L->n) { ERROR (CHOLMOD_INVALID, "leading dimension smaller than n") ; return FALSE ; }
+    const size_t annz = (size_t) ((Int *) A->p) [A->ncol] ;
+    if (annz > 0 && !A->i) { ERROR (CHOLMOD_INVALID, "argument missing") ; return FALSE ; }
+    if (!gr_factor_ready (L, FALSE, Common)) return FALSE ;
+    if (!L->hip_apat_valid)
+    { ERROR (CHOLMOD_INVALID, "L holds no pattern record: cholmod_l_factorize from a host matrix of this pattern first") ; return FALSE ; }
+    /* the proof that the plan's value map fits A, as in cholmod_l_hip_selinv_device: a mismatch touches no device state */
+    uint64_t hash [2] ;
+    hash [0] = ssamd_pattern_hash (A, &hash [1]) ;
+    if (L->hip_apat_nnz != annz || L->hip_apat_hash != hash [0] || L->hip_apat_hash2 != hash [1])
+    { ERROR (CHOLMOD_INVALID, "A does not have the pattern L was last factorized from") ; return FALSE ; }
+    Common->status = CHOLMOD_OK ;
+    if (L->n == 0 || annz == 0) return TRUE ;
+    cholmod_hip_plan *plan = (cholmod_hip_plan *) L->hip_plan ;
+    if (!L->hip_perm_set)
+    {
+        int rc = cholmod_hip_set_perm (plan, (const int64_t *) L->Perm) ;
+        if (rc != CHOLMOD_HIP_OK) return gr_status (rc, Common, "the permutation could not be stored on the device") ;
+        L->hip_perm_set = TRUE ;
+    }
+    return gr_status (cholmod_hip_values_grad_device (plan, 1, alpha, U_dev, (int64_t) ldu, V_dev, (int64_t) ldv,
+        (int64_t) nrhs, G_dev, (int64_t) annz, stream), Common, "the plan holds no value map for this matrix") ;
+}
+
+int cholmod_l_hip_logdet_device (cholmod_factor *L, double *out_dev, void *stream, cholmod_common *Common)
+{
+    RETURN_IF_NULL_COMMON (FALSE) ;
+    RETURN_IF_NULL (L, FALSE) ;
+    RETURN_IF_NULL (out_dev, FALSE) ;
+    if (!gr_factor_ready (L, TRUE, Common)) return FALSE ;
+    Common->status = CHOLMOD_OK ;
+    return gr_status (cholmod_hip_logdet_device ((cholmod_hip_plan *) L->hip_plan, out_dev, stream), Common,
+        "the plan holds no positive definite factor on the device") ;
+}
