@@ -457,6 +457,31 @@ int cholmod_l_hip_selinv_to_host (cholmod_factor *L, double *Zx, cholmod_common 
 int cholmod_l_hip_values_grad_device (cholmod_sparse *A, cholmod_factor *L, double alpha, const double *U_dev, size_t ldu,
     const double *V_dev, size_t ldv, size_t nrhs, double *G_dev, void *stream, cholmod_common *Common) ;
 int cholmod_l_hip_logdet_device (cholmod_factor *L, double *out_dev, void *stream, cholmod_common *Common) ;
+/* The same two gradients for an UNSYMMETRIC A (stype == 0), through L L' = M = A*A' + beta*I as
+ * cholmod_l_hip_factorize_values_device forms it: the gradient with respect to the nnz (A) values of A, in A's entry order.
+ * Avalues_dev: the values L was factorized from (nnz (A) doubles on the device, read only; A->x is never read), G_dev:
+ * nnz (A) doubles on the device, all written.
+ * cholmod_l_hip_aat_values_grad_device: with G = alpha (U V' + V U') sampled on tril (M) as above (twice off the diagonal),
+ *     G_dev [q] = sum over the entries (j, k) of column k of the entry q = (i, k):  G (i, j) a (j, k)       (2 G (i, i) a_q at j == i)
+ * -- with U = Lambda = M^-1 gX, V = X = M^-1 B and alpha = -1 the gradient of a scalar through the solve, -(Lambda X' +
+ * X Lambda') A sampled on A; the gradient with respect to beta is alpha sum_r sum_i U [i, r] V [i, r], a reduction the caller
+ * forms.  cholmod_l_hip_aat_logdet_grad_device: the gradient of log det M, 2 (Z A) sampled on A with Z = M^-1 the selected
+ * inverse, computed now if the resident one is stale; with respect to beta it is trace Z (cholmod_l_hip_selinv_device's
+ * diag_dev, summed).
+ * The product map is built by the first call for this pattern if cholmod_l_hip_factorize_values_device has not built it
+ * (the same host pass), its transpose by the first gradient call after that: one download of the lists, a counting pass
+ * on the host, 16 more bytes of HBM per pair; a caller who never differentiates pays nothing.  Ordered on `stream`; one
+ * owner per entry of G_dev, a fixed summation order, no floating-point atomics: the same inputs give the same bits.
+ * FALSE with CHOLMOD_INVALID for NULL pointers, a SYMMETRIC A (stype != 0: cholmod_l_hip_values_grad_device), an unpacked A,
+ * A->nrow != L->n, a leading dimension smaller than n, a symbolic L, the GPU switched off (no host fallback), several
+ * ranks, an L not factorized on the device or without the pattern record, an A*A' of another pattern than L was factorized
+ * from (an fset is not supported) -- the log-determinant also for L->minor < n --, with CHOLMOD_NOT_INSTALLED for a
+ * complex or zomplex A or L: all before a device is touched. */
+int cholmod_l_hip_aat_values_grad_device (cholmod_sparse *A, cholmod_factor *L, double alpha, const double *U_dev, size_t ldu,
+    const double *V_dev, size_t ldv, size_t nrhs, const double *Avalues_dev, double *G_dev, void *stream,
+    cholmod_common *Common) ;
+int cholmod_l_hip_aat_logdet_grad_device (cholmod_sparse *A, cholmod_factor *L, const double *Avalues_dev, double *G_dev,
+    void *stream, cholmod_common *Common) ;
 /* cholmod_l_factorize for new VALUES of A that already live in device memory (a matrix assembled on the GPU: the step of a
  * Newton, time-stepping or interior-point loop), without a trip through the host.  A supplies the PATTERN only (p, i,
  * stype, packed; A->x is never read and may be NULL); Ax_dev is a device pointer to nnz (A) doubles in A's own entry

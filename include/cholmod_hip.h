@@ -452,6 +452,34 @@ int cholmod_hip_values_grad_device (cholmod_hip_plan *plan, int perm, double alp
  * device call: a NULL plan or pointer, a host-only plan, several ranks, no numeric factor on the device, a last
  * factorization that was not positive definite, the plans of complex factors. */
 int cholmod_hip_logdet_device (cholmod_hip_plan *plan, double *dOut, void *stream) ;
+/* The same two gradients THROUGH A PRODUCT MAP (cholmod_hip_set_product_map: the resident S = tril (A A') is computed from
+ * the navalues values a of the caller's array, M = A A' + beta I): the gradient with respect to a.  With Gv [c] the gradient
+ * with respect to value c of the value map -- the sampled product above for a solve; Z once on the diagonal and twice off
+ * it for log det M; +0.0 where the resident S does not read the value, never the NaN of the selected inverse's gather --
+ *     dGa [q] = sum_{p : ia [p] = q} Gv [c (p)] a [ib [p]]  +  sum_{p : ib [p] = q} Gv [c (p)] a [ia [p]]
+ * (a pair with ia [p] == ib [p] == q is in both sums).  Gv goes into a scratch of the plan (nc doubles), by the kernels of
+ * cholmod_hip_values_grad_device or by the gather of the selected inverse; k_product_grad, the transpose of
+ * k_product_values, then reads it and dA (navalues doubles on the device, the values the factor was computed from, read
+ * only) into dGa: a group of 1, 16 or 64 lanes owns one q, by the length of its list, and adds its half-pairs in a fixed
+ * order -- no floating-point atomics, the same inputs give the same bits.  All of dGa [0 .. navalues) is written; a value
+ * that is in no pair receives +0.0.
+ * The TRANSPOSED MAP (per value q its half-pairs (c, partner): 16 bytes of HBM per pair, as the forward map) is built by
+ * the first of these calls after a cholmod_hip_set_product_map -- the forward lists are downloaded once, one stable
+ * counting pass on the host, one upload; that call waits for the host -- and freed with the map: a caller who never
+ * differentiates pays nothing.  After it nothing is allocated and the host does not wait.  Ordered on `stream` exactly as
+ * cholmod_hip_values_grad_device is (not during capture).
+ * cholmod_hip_product_logdet_grad_device needs a current selected inverse (cholmod_hip_selinv_device after the last
+ * factorization).
+ * CHOLMOD_HIP_INVALID, before any device call: a NULL plan or pointer, a host-only plan, several ranks, the plans of complex
+ * factors, ld < n, nrhs < 0, NO product map set, navalues other than the product map's, no value map for the current
+ * resident S, perm without a stored permutation; for the log-determinant no current selected inverse or a last
+ * factorization that was not positive definite.  nrhs == 0 is a success that zero-fills dGa; n == 0 or navalues == 0
+ * touches nothing.  cholmod_hip_values_grad_device and cholmod_hip_selinv_gather_device go on refusing a plan with a
+ * product map: their output is in the order of the value map, which is not the caller's array then. */
+int cholmod_hip_product_values_grad_device (cholmod_hip_plan *plan, int perm, double alpha, const double *dU, int64_t ldu,
+    const double *dV, int64_t ldv, int64_t nrhs, const double *dA, double *dGa, int64_t navalues, void *stream) ;
+int cholmod_hip_product_logdet_grad_device (cholmod_hip_plan *plan, const double *dA, double *dGa, int64_t navalues,
+    void *stream) ;
 
 /* Parity hooks: copy derived integer maps back to the host.
  *  sparent  [nsuper]     supernodal etree (reference :1025)

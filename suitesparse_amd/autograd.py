@@ -2,22 +2,30 @@
 the device and on torch's current stream.
 
     chol = DeviceCholesky(session, A, Lf, beta=0.0)
-    X = chol.solve(values, B)           # (A (values) + beta I)^-1 B; differentiable in values and B
-    ld = chol.logdet(values)            # log det (A (values) + beta I); differentiable in values
+    X = chol.solve(values, B)           # M^-1 B; differentiable in values, B and (a tensor) beta
+    ld = chol.logdet(values)            # log det M; differentiable in values and (a tensor) beta
 
 `A` gives the pattern, `values` (a 1-D torch.float64 device tensor of length nnz (A), A's entry order) the numbers, `Lf` is a
-factor that was factorized once from a host matrix of A's pattern -- the precondition of Session.factorize_device.
+factor that was factorized once from a host matrix of A's pattern -- the precondition of Session.factorize_device.  For a
+symmetric A (stype != 0) M = A (values) + beta I; for an unsymmetric one (stype == 0) M = A (values) A (values)' + beta I,
+the normal equations of a least-squares problem with A = J' and beta the damping.
 
-With X = M^-1 B, M = A + beta I, and an incoming gradient gX:  Lambda = M^-1 gX  is the gradient with respect to B, and
--(Lambda X' + X Lambda') sampled on the entries of A the factorization reads (Session.values_grad_device) the one with
-respect to the values; a value the factorization does not read (the ignored triangle of a symmetric A) has gradient zero.
-The gradient of log det M with respect to the value at (i, j) is Z_ii on the diagonal and 2 Z_ij off it, Z = M^-1 from
-Session.selinv_device.
+With X = M^-1 B and an incoming gradient gX:  Lambda = M^-1 gX  is the gradient with respect to B, and
+-(Lambda X' + X Lambda') is the one with respect to M: sampled on the entries of A the factorization reads
+(Session.values_grad_device) it is the gradient with respect to the values of a symmetric A -- a value the factorization
+does not read (the ignored triangle) has gradient zero --, carried through the product map (Session.aat_values_grad_device)
+the one with respect to the values of an unsymmetric A; its trace, -(Lambda . X).sum (), the one with respect to beta.
+The gradient of log det M with respect to M is Z = M^-1 from Session.selinv_device: Z_ii on the diagonal and 2 Z_ij off it
+for the value of a symmetric A at (i, j), Session.aat_logdet_grad_device for an unsymmetric A, Z's trace for beta.
+
+beta is a Python float, or a 0-dim torch.float64 tensor on either device; a tensor that requires grad receives its
+gradient (two torch reductions on the current stream).  The factorization reads float (beta) -- it waits for the host
+anyway --, once per version of the tensor.
 
 The wrapper OWNS Lf: a factorization of Lf behind its back is detected (the engine counts factorizations,
 cholmod_hip_progress out [0]) and answered by factorizing again from the values a backward pass saved, but values handed to
 Session.factorize_device directly are not seen by `solve` / `logdet` calls that follow with the tensor factorized last.
-beta is a Python float and is not differentiated; both functions are differentiable once; real factors, one rank."""
+Both functions are differentiable once; real factors, one rank."""
 import ctypes as C
 
 import numpy as np
@@ -29,12 +37,40 @@ from . import cholmod as ch
 
 class DeviceCholesky:
     def __init__(self, session, A, Lf, beta=0.0):
-        self.S, self.A, self.Lf, self.beta = session, A, Lf, float(beta)
+        self.S, self.A, self.Lf = session, A, Lf
+        self.aat = A.contents.stype == 0        # M = A A' + beta I
+        self.beta = beta
         self._values = None         # the tensor factorized last (kept alive: its address cannot be handed out again)
         self._key = None            # (data_ptr, _version, beta) of that factorization
         self._fact = -1             # the engine's count of factorizations right after it
         self._mult = None
         self.factorizations = 0     # ... and the wrapper's own
+
+    # ---- beta: a float, or a 0-dim float64 tensor that is read once per version
+    @property
+    def beta(self):
+        return self._beta
+
+    @beta.setter
+    def beta(self, beta):
+        if isinstance(beta, torch.Tensor):
+            if beta.dim() != 0 or beta.dtype != torch.float64:
+                raise TypeError("DeviceCholesky: a tensor beta must be 0-dim and torch.float64")
+            self._beta, self._beta_read = beta, None
+        else:
+            self._beta, self._beta_read = float(beta), None
+
+    def _beta_value(self):
+        b = self._beta
+        if not isinstance(b, torch.Tensor):
+            return b
+        if self._beta_read is None or self._beta_read[0] != b._version:
+            self._beta_read = (b._version, float(b.detach()))
+        return self._beta_read[1]
+
+    def _beta_input(self):
+        """what the autograd functions take as their beta input: the tensor, or None for a float"""
+        return self._beta if isinstance(self._beta, torch.Tensor) else None
 
     # ---- the factor
     def _count(self):
@@ -48,17 +84,18 @@ class DeviceCholesky:
 
     def _factorize(self, values):
         self._key = self._values = None
-        ok = self.S.factorize_device(self.A, values, self.Lf, self.beta)
+        beta = self._beta_value()
+        ok = self.S.factorize_device(self.A, values, self.Lf, beta)
         if not ok or self.S.cm.status != ch.OK or self.Lf.contents.minor < self.Lf.contents.n:
             raise RuntimeError(f"DeviceCholesky: the matrix is not positive definite or the factorization failed "
                                f"(status {self.S.cm.status}, minor {self.Lf.contents.minor})")
         self.factorizations += 1
-        self._values, self._key, self._fact = values, (values.data_ptr(), values._version, self.beta), self._count()
+        self._values, self._key, self._fact = values, (values.data_ptr(), values._version, beta), self._count()
 
     def _ensure(self, values):
         """the factor of `values`: reused when `values` is the tensor factorized last, unchanged, and Lf still holds it"""
         values = values.detach()
-        if self._key != (values.data_ptr(), values._version, self.beta) or self._count() != self._fact:
+        if self._key != (values.data_ptr(), values._version, self._beta_value()) or self._count() != self._fact:
             self._factorize(values)
         return self._fact
 
@@ -81,18 +118,19 @@ class DeviceCholesky:
 
     # ---- the differentiable functions
     def solve(self, values, B):
-        """X = (A (values) + beta I)^-1 B; B of shape (nrhs, n) or (n,), rows are right-hand sides (Session.solve_device)"""
-        return _Solve.apply(self, values, B)
+        """X = M^-1 B; B of shape (nrhs, n) or (n,), rows are right-hand sides (Session.solve_device)"""
+        return _Solve.apply(self, values, B, self._beta_input())
 
     def logdet(self, values):
-        """log det (A (values) + beta I) as a 0-dim device tensor"""
-        return _LogDet.apply(self, values)
+        """log det M as a 0-dim device tensor"""
+        return _LogDet.apply(self, values, self._beta_input())
 
 
 class _Solve(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, chol, values, B):
+    def forward(ctx, chol, values, B, beta):
         ctx.chol, ctx.fact = chol, chol._ensure(values)
+        ctx.beta_device = None if beta is None else beta.device
         X = chol.S.solve_device(chol.Lf, B.detach().contiguous())
         ctx.save_for_backward(values, X)
         return X
@@ -102,19 +140,25 @@ class _Solve(torch.autograd.Function):
     def backward(ctx, gX):
         chol = ctx.chol
         values, X = ctx.saved_tensors
-        need_v, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        if not (need_v or need_b):
-            return None, None, None
+        need_v, need_b, need_beta = ctx.needs_input_grad[1:4]
+        if not (need_v or need_b or need_beta):
+            return None, None, None, None
         chol._restore(values, ctx.fact)
         lam = chol.S.solve_device(chol.Lf, gX.contiguous())
-        gv = chol.S.values_grad_device(chol.A, chol.Lf, lam, X, alpha=-1.0) if need_v else None
-        return None, gv, (lam if need_b else None)
+        gv = None
+        if need_v and chol.aat:
+            gv = chol.S.aat_values_grad_device(chol.A, chol.Lf, values.detach(), lam, X, alpha=-1.0)
+        elif need_v:
+            gv = chol.S.values_grad_device(chol.A, chol.Lf, lam, X, alpha=-1.0)
+        gbeta = (-(lam * X).sum()).to(ctx.beta_device) if need_beta else None
+        return None, gv, (lam if need_b else None), gbeta
 
 
 class _LogDet(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, chol, values):
+    def forward(ctx, chol, values, beta):
         ctx.chol, ctx.fact = chol, chol._ensure(values)
+        ctx.beta_device = None if beta is None else beta.device
         ctx.save_for_backward(values)
         return chol.S.logdet_device(chol.Lf)
 
@@ -123,9 +167,17 @@ class _LogDet(torch.autograd.Function):
     def backward(ctx, g):
         chol = ctx.chol
         (values,) = ctx.saved_tensors
-        if not ctx.needs_input_grad[1]:
-            return None, None
+        need_v, need_beta = ctx.needs_input_grad[1:3]
+        if not (need_v or need_beta):
+            return None, None, None
         chol._restore(values, ctx.fact)
-        Z, _ = chol.S.selinv_device(chol.A, chol.Lf, diag=False)
-        Z = torch.where(torch.isnan(Z), torch.zeros_like(Z), Z)
-        return None, g * chol._multiplier(Z.device) * Z
+        gv = gbeta = None
+        if need_v and chol.aat:
+            gv = g * chol.S.aat_logdet_grad_device(chol.A, chol.Lf, values.detach())
+        elif need_v:
+            Z, _ = chol.S.selinv_device(chol.A, chol.Lf, diag=False)
+            Z = torch.where(torch.isnan(Z), torch.zeros_like(Z), Z)
+            gv = g * chol._multiplier(Z.device) * Z
+        if need_beta:
+            gbeta = (g * chol.S.selinv_device(None, chol.Lf, values=False, diag=True)[1].sum()).to(ctx.beta_device)
+        return None, gv, gbeta

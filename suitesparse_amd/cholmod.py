@@ -151,6 +151,7 @@ API_SYMBOLS = [
     "cholmod_l_hip_factorize_values_device", "cholmod_l_hip_aat_product_map",
     "cholmod_l_hip_selinv_device", "cholmod_l_hip_selinv_to_host",
     "cholmod_l_hip_values_grad_device", "cholmod_l_hip_logdet_device",
+    "cholmod_l_hip_aat_values_grad_device", "cholmod_l_hip_aat_logdet_grad_device",
 ]
 HIP_SYMBOLS = [
     "cholmod_hip_probe", "cholmod_hip_memorysize", "cholmod_hip_set_device", "cholmod_hip_device_count",
@@ -167,6 +168,7 @@ HIP_SYMBOLS = [
     "cholmod_hip_selinv_device", "cholmod_hip_selinv_gather_device", "cholmod_hip_selinv_download",
     "cholmod_hip_selinv_release", "cholmod_hip_selinv_info",
     "cholmod_hip_values_grad_device", "cholmod_hip_logdet_device",
+    "cholmod_hip_product_values_grad_device", "cholmod_hip_product_logdet_grad_device",
     "cholmod_hip_dense_partial_factor", "cholmod_hip_factor_checks", "cholmod_hip_factor_checks_local", "cholmod_hip_get_launch_profile", "cholmod_hip_debug_thin_cycles", "cholmod_hip_debug_launch_regions",
     "cholmod_hip_debug_cb_extend_add", "cholmod_hip_debug_fused_pair",
     "cholmod_hip_rccl_unique_id", "cholmod_hip_rccl_attach", "cholmod_hip_rccl_detach",
@@ -317,6 +319,10 @@ def lib(hooks=None):
     sig("cholmod_hip_logdet_device", C.c_int, [vp, vp, vp])
     sig("cholmod_l_hip_values_grad_device", C.c_int, [sp, fc, dbl, vp, sz, vp, sz, sz, vp, vp, cm])
     sig("cholmod_l_hip_logdet_device", C.c_int, [fc, vp, vp, cm])
+    sig("cholmod_hip_product_values_grad_device", C.c_int, [vp, C.c_int, dbl, vp, i64, vp, i64, i64, vp, vp, i64, vp])
+    sig("cholmod_hip_product_logdet_grad_device", C.c_int, [vp, vp, vp, i64, vp])
+    sig("cholmod_l_hip_aat_values_grad_device", C.c_int, [sp, fc, dbl, vp, sz, vp, sz, sz, vp, vp, vp, cm])
+    sig("cholmod_l_hip_aat_logdet_grad_device", C.c_int, [sp, fc, vp, vp, vp, cm])
     sig("cholmod_hip_get_maps", C.c_int, [vp, vp, vp, vp])
     sig("cholmod_hip_get_stats", C.c_int, [vp, vp])
     sig("cholmod_hip_set_profiling", C.c_int, [vp, C.c_int])
@@ -646,6 +652,61 @@ class Session:
                                                      nrhs, out.data_ptr() or 2, stream, C.byref(self.cm))
         if not ok:
             raise RuntimeError(f"cholmod_l_hip_values_grad_device failed, status {self.cm.status}")
+        return out
+
+    @staticmethod
+    def _aat_values(what, A, values, out):
+        """(nnz (A), out) for the gradients through A*A': `values` and `out` 1-D contiguous torch.float64 tensors of
+        length nnz (A) on one device; out=None: a new tensor"""
+        import torch
+        a = A.contents
+        nz = int(_view(a.p, a.ncol + 1, C.c_int64, np.int64)[-1]) if a.p else 0
+        if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float64):
+            raise TypeError(f"{what}: values must be a torch.float64 tensor on the device")
+        if values.dim() != 1 or values.shape[0] != nz or not values.is_contiguous():
+            raise ValueError(f"{what}: values must be 1-D, contiguous and of length nnz (A) = {nz}")
+        if out is None:
+            out = torch.empty(nz, dtype=torch.float64, device=values.device)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.device == values.device):
+            raise ValueError(f"{what}: out must be a torch.float64 tensor on the device of values")
+        if out.dim() != 1 or out.shape[0] != nz or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be 1-D, contiguous and of length nnz (A) = {nz}")
+        return nz, out
+
+    def aat_values_grad_device(self, A, Lf, values, U, V, alpha=1.0, out=None):
+        """cholmod_l_hip_aat_values_grad_device: for an unsymmetric A (stype 0) and M = A A' + beta I, the chain rule from
+        G = alpha (U V' + V U') sampled on tril (M) to the values of A: out [q] = sum_j G (i, j) a (j, k) over column k of
+        the entry q = (i, k).  With U = M^-1 gX, V = X = M^-1 B and alpha = -1 the gradient of a scalar with respect to
+        A's values through the solve.  values: the 1-D device tensor Lf was factorized from (factorize_device); U, V as
+        for `values_grad_device`.  Returns a 1-D tensor of length nnz (A) in A's entry order, or writes into `out`.
+        Enqueued on torch's current stream; the same inputs give the same bits.  The first call after a new pattern
+        builds the transposed product map on the host and waits for it."""
+        import torch
+        n = int(Lf.contents.n)
+        ldu, nrhs = self._device_layout("aat_values_grad_device: U", n, U)
+        ldv, _ = self._device_layout("aat_values_grad_device: V", n, V, like=U)
+        _, out = self._aat_values("aat_values_grad_device", A, values, out)
+        if values.device != U.device:
+            raise ValueError("aat_values_grad_device: values must be on the device of U")
+        stream = torch.cuda.current_stream(U.device).cuda_stream
+        ok = self.L.cholmod_l_hip_aat_values_grad_device(A, Lf, float(alpha), U.data_ptr() or 1, ldu, V.data_ptr() or 1, ldv,
+                                                         nrhs, values.data_ptr() or 3, out.data_ptr() or 2, stream,
+                                                         C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_aat_values_grad_device failed, status {self.cm.status}")
+        return out
+
+    def aat_logdet_grad_device(self, A, Lf, values, out=None):
+        """cholmod_l_hip_aat_logdet_grad_device: the gradient of log det (A A' + beta I) with respect to the values of the
+        unsymmetric A, 2 (Z A) sampled on A with Z the selected inverse (computed if the resident one is stale).  Tensors,
+        stream and result as for `aat_values_grad_device`."""
+        import torch
+        _, out = self._aat_values("aat_logdet_grad_device", A, values, out)
+        stream = torch.cuda.current_stream(values.device).cuda_stream
+        ok = self.L.cholmod_l_hip_aat_logdet_grad_device(A, Lf, values.data_ptr() or 3, out.data_ptr() or 2, stream,
+                                                         C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_aat_logdet_grad_device failed, status {self.cm.status}")
         return out
 
     def logdet_device(self, Lf):

@@ -15,6 +15,11 @@ static void drop_product_map (cholmod_hip_plan *P)
     for (void *d : {(void *) P->d_pm_cp, (void *) P->d_pm_ia, (void *) P->d_pm_ib, (void *) P->d_pm_order}) if (d) (void) hipFree (d) ;
     P->d_pm_cp = P->d_pm_ia = P->d_pm_ib = nullptr ; P->d_pm_order = nullptr ;
     P->pm_set = false ; P->pm_na = 0 ;
+    /* ... and its transpose, where a gradient call has built it (grad.hip) */
+    for (void *d : {(void *) P->d_pt_ptr, (void *) P->d_pt_c, (void *) P->d_pt_partner, (void *) P->d_pt_order, (void *) P->d_pt_gvals})
+        if (d) (void) hipFree (d) ;
+    P->d_pt_ptr = nullptr ; P->d_pt_c = P->d_pt_partner = P->d_pt_order = nullptr ; P->d_pt_gvals = nullptr ;
+    P->pt_built = false ;
 }
 
 static void free_device (cholmod_hip_plan *P)

@@ -1,5 +1,6 @@
 // grad_kernels.hip.h -- device code of grad.hip: the gradient of a scalar with respect to the values of A, sampled on
-// the pattern of the resident S (cholmod_hip_values_grad_device), and log det of the resident factor
+// the pattern of the resident S (cholmod_hip_values_grad_device), the chain rule from there through a product map to the
+// values of an unsymmetric A (k_product_grad: cholmod_hip_product_*_grad_device), and log det of the resident factor
 // (cholmod_hip_logdet_device).
 //
 // The gradient is a sampled product: for entry p = (i, j) of S that the factorization reads (the rule of
@@ -105,6 +106,38 @@ __global__ void __launch_bounds__(256) k_gr_panel (i64 n, i64 nz, const i64 *Sp,
         const double s = first ? mine : G [k] + mine ;
         G [k] = last ? alpha * s : s ;
     }
+}
+
+// ---- the chain rule through a product map: the transpose of k_product_values (kernels.hip.h) -------------------------------
+//
+// vals [c] = sum over the pairs p of list c of a [ia [p]] a [ib [p]], and Gv [c] = d loss / d vals [c]; then
+//     g [q] = sum_{p : ia [p] = q} Gv [c (p)] a [ib [p]]  +  sum_{p : ib [p] = q} Gv [c (p)] a [ia [p]]
+// (a pair with ia [p] == ib [p] == q is in both sums: the 2 a_q of a square).  The transposed map stores, per value q, these
+// half-pairs as (tc [h], tpart [h]), tp [q] <= h < tp [q + 1], in ascending p, the ia half of a pair before its ib half:
+// 16 bytes per pair, as the forward map.  The values come sorted by list length into the classes of the forward kernel
+// (order [g]: the value group g of this launch owns; PM_LEN1, PM_LEN16) and a group of G lanes owns one value: lane l adds
+// the half-pairs l, l + G, ... in that order (fused multiply-add), the G partial sums meet in a butterfly of fixed shape and
+// lane 0 stores -- one owner per g [q], the order a function of the map alone, no floating-point atomic: the same inputs give
+// the same bits.  A value in no pair has an empty list and gets +0.0.  Two dependent gathers per half-pair (8-byte Gv and
+// a, scattered) behind two coalesced 4-byte index loads: latency and bandwidth, nothing for the matrix cores.  Every index
+// was checked on the host when the forward map was set: nothing outside Gv [0 .. nc) and a [0 .. navalues) is read.
+template <int G>
+__global__ void __launch_bounds__(256) k_product_grad (i64 ngroups, const i32 *order, const i64 *tp, const i32 *tc, const i32 *tpart,
+    const double *Gv, const double *a, double *g)
+{
+    const i64 t = blockIdx.x * (i64) 256 + threadIdx.x ;
+    const i64 grp = t / G ;
+    const int l = (int) (t % G) ;
+    // (a whole group leaves together: the shuffles below see the lanes of live groups only)
+    if (grp >= ngroups) return ;
+    const i64 q = order [grp] ;
+    const i64 h1 = tp [q + 1] ;
+    double acc = 0.0 ;
+#pragma unroll 2
+    for (i64 h = tp [q] + l ; h < h1 ; h += G) acc = __builtin_fma (Gv [tc [h]], a [tpart [h]], acc) ;
+#pragma unroll
+    for (int w = G / 2 ; w > 0 ; w >>= 1) acc += __shfl_xor (acc, w, 64) ;
+    if (l == 0) g [q] = acc ;
 }
 
 // ---- log det of the resident factor: 2 sum_j log L_jj, two fixed-order stages, no atomics ---------------------------------

@@ -185,9 +185,7 @@ __global__ void __launch_bounds__(256) k_values_chunk (i64 k0, i64 k1, const i64
 // Lane l of a group adds the pairs l, l + G, l + 2 G, ... in that order (fused multiply-add), then the G partial sums
 // meet in a butterfly of fixed shape: one owner per entry, the order a function of the list alone, no floating-point
 // atomic -- the same values give the same bits, as in residual_kernels.hip.h.  Every index was checked on the host when
-// the map was set: nothing outside a [0 .. navalues) is read.
-#define PM_LEN1 8
-#define PM_LEN16 128
+// the map was set: nothing outside a [0 .. navalues) is read.  (PM_LEN1, PM_LEN16: descriptors.hip.h)
 template <int G>
 __global__ void __launch_bounds__(256) k_product_values (i64 ngroups, const i32 *order, const i64 *cp, const i64 *ia, const i64 *ib,
     const double *a, double *vals)

@@ -361,6 +361,15 @@ struct cholmod_hip_plan {
     i64 *d_pm_cp = nullptr, *d_pm_ia = nullptr, *d_pm_ib = nullptr ; i32 *d_pm_order = nullptr ;
     i64 pm_class [4] = {0, 0, 0, 0}, pm_na = 0 ;
     bool pm_set = false ;
+    // the transposed product map (grad.hip: built by the first gradient call after a cholmod_hip_set_product_map, freed
+    // with the map): per value q of the caller's array the half-pairs (entry c of the value map, partner value) it takes
+    // part in, pt_ptr [q] .. pt_ptr [q+1], in ascending pair; the values sorted by list length into the classes of
+    // k_product_grad (pt_order, pt_class); and the gradient with respect to the vals_n values of the value map
+    // (pt_gvals), the scratch between the sampled product or the gather of Z and k_product_grad
+    i64 *d_pt_ptr = nullptr ; i32 *d_pt_c = nullptr, *d_pt_partner = nullptr, *d_pt_order = nullptr ;
+    double *d_pt_gvals = nullptr ;
+    i64 pt_class [4] = {0, 0, 0, 0} ;
+    bool pt_built = false ;
     double *h_vals = nullptr ; i64 h_vals_n = 0 ;           // pinned staging of the value upload (cholmod_hip_values_begin)
     // the upload is staged / pushed chunk by chunk; in batch order the entries of S are sorted by the batch of their column's
     // front (cholmod_hip_set_value_map) and a batch waits for its own chunks only, in S order the assembly waits for all
@@ -422,6 +431,10 @@ static inline const FrontD *whole_fronts (cholmod_hip_plan *P) { return P->world
 
 // selinv.hip: everything the selected inverse holds of a plan (cholmod_hip_plan_destroy)
 void selinv_free (cholmod_hip_plan *P) ;
+// selinv.hip: out [src [p]] = Z at every entry p of the resident S that is read, once on the diagonal and twice off it,
+// enqueued on `st` (grad.hip: the gradient of the log-determinant with respect to the values of the value map; the
+// caller has checked si_valid, filled `out` with +0.0 and passes its column-of-entry array of the resident S)
+void selinv_gather_logdet_grad (cholmod_hip_plan *P, const i32 *colof, double *out, hipStream_t st) ;
 // grad.hip: likewise
 void grad_free (cholmod_hip_plan *P) ;
 

@@ -284,6 +284,14 @@ void selinv_free (cholmod_hip_plan *P)
     delete S ;
 }
 
+void selinv_gather_logdet_grad (cholmod_hip_plan *P, const i32 *colof, double *out, hipStream_t st)
+{
+    const i64 nz = P->s_cur_nz ;
+    if (nz > 0)
+        hipLaunchKernelGGL (k_si_gather_logdet_grad, dim3 ((unsigned) ((nz + 255) / 256)), dim3 (256), 0, st, P->n, nz, P->d_Sp, P->d_Si,
+            colof, P->d_vsrc, P->d_supermap, P->d_fr, P->d_Ls, P->si->d_Zx, out) ;
+}
+
 extern "C" {
 
 int cholmod_hip_selinv_device (cholmod_hip_plan *P, void *stream)

@@ -343,6 +343,23 @@ __global__ void __launch_bounds__(256) k_si_gather_values (i64 n, const i64 *Sp,
     }
 }
 
+// The variant of grad.hip (cholmod_hip_product_logdet_grad_device): the gradient of log det with respect to the value of
+// entry p -- Z once on the diagonal, twice off it -- into an array the caller has filled with +0.0: where the gather above
+// leaves the NaN of its fill, this one leaves the zero, so that no NaN enters a sum.  Work is divided by ENTRIES of S, as
+// in grad_kernels.hip.h, with the column of an entry from grad.hip's column-of-entry array: S = tril (A A') has columns of
+// hundreds of entries next to columns of one (one thread per column took 1.05 ms where this takes 26 us: a grid
+// least-squares problem with eight dense rows, profiles/aat_grad_times.json).
+__global__ void __launch_bounds__(256) k_si_gather_logdet_grad (i64 n, i64 nz, const i64 *Sp, const i64 *Si, const i32 *colof,
+    const i64 *src, const i32 *supermap, const FrontD *fr, const i64 *Ls, const double *Zx, double *out)
+{
+    const i64 p = blockIdx.x * (i64) 256 + threadIdx.x ;
+    if (p >= nz) return ;
+    const i64 k = colof [p], i = Si [p] ;
+    if (i < k || i >= n || (p + 1 < Sp [k + 1] && Si [p + 1] == i)) return ;
+    const i64 q = si_locate (fr [supermap [k]], Ls, i, k) ;
+    if (q >= 0) out [src [p]] = i != k ? 2.0 * Zx [q] : Zx [q] ;
+}
+
 // out [perm ? perm [k] : k] = Z (k, k)
 __global__ void __launch_bounds__(256) k_si_gather_diag (i64 n, const i64 *perm, const i32 *supermap, const FrontD *fr,
     const double *Zx, double *out)

@@ -54,6 +54,9 @@ int ssamd_resolve_use_gpu (cholmod_common *Common) ;
 int ssamd_ensure_plan (cholmod_factor *L, cholmod_common *Common) ;
 /* the two fingerprints of A's pattern that L->hip_apat_hash / hip_apat_hash2 record (numeric.c) */
 uint64_t ssamd_pattern_hash (cholmod_sparse *A, uint64_t *second) ;
+/* the product map of the resident tril (A*A') of L's plan set for the unsymmetric A (annz entries, pattern hash `hash`);
+ * built on first use (numeric.c) */
+int ssamd_aat_product_map_ready (cholmod_sparse *A, cholmod_factor *L, size_t annz, const uint64_t hash [2], cholmod_common *Common) ;
 void ssamd_plan_ahead (cholmod_factor *L, cholmod_common *Common, const int64_t *reach_p, const int32_t *reach_first) ;
 int64_t ssamd_front_reach (const cholmod_sparse *U, const cholmod_factor *L, int64_t *reach_p, int32_t *reach_first) ;
 void ssamd_front_reach_alloc (const cholmod_sparse *U, const cholmod_factor *L, int64_t **reach_p, int32_t **reach_first) ;

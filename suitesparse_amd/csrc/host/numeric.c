@@ -766,6 +766,47 @@ int cholmod_l_factorize_p (cholmod_sparse *A, double beta [2], SuiteSparse_long 
     return ok ;
 }
 
+/* The product map of the resident tril (A*A') of L's plan (cholmod_hip_set_product_map), for the unsymmetric A whose pattern
+ * hashes to `hash` and has annz entries: built by the first call for that pattern -- cholmod_l_hip_factorize_values_device or
+ * a gradient through it (grad.c) --, a comparison of three numbers after that.  TRUE: the map is set for A
+ * (L->hip_aat_valid); FALSE with Common->status set: A*A' does not have the pattern L was last factorized from, or the map
+ * could not be built. */
+int ssamd_aat_product_map_ready (cholmod_sparse *A, cholmod_factor *L, size_t annz, const uint64_t hash [2], cholmod_common *Common)
+{
+    if (L->hip_aat_valid && L->hip_aat_nnz == annz && L->hip_aat_hash == hash [0] && L->hip_aat_hash2 == hash [1]) return TRUE ;
+    /* the resident matrix is tril (A*A'): its pattern from A's, against the record; then the lists of products */
+    cholmod_sparse *Cm = ssamd_aat (A, NULL, 0, TRUE, Common) ;
+    if (!Cm) return FALSE ;
+    uint64_t chash [2] ;
+    chash [0] = pattern_hash (Cm, &chash [1]) ;
+    const size_t cnz = (size_t) ((Int *) Cm->p) [Cm->ncol] ;
+    cholmod_l_free_sparse (&Cm, Common) ;
+    if (L->hip_apat_nnz != cnz || L->hip_apat_hash != chash [0] || L->hip_apat_hash2 != chash [1])
+    { ERROR (CHOLMOD_INVALID, "A*A' does not have the pattern L was last factorized from") ; return FALSE ; }
+    const int64_t npairs = cholmod_l_hip_aat_product_map (A, NULL, NULL, NULL, Common) ;
+    if (npairs < 0) return FALSE ;
+    if (npairs > INT32_MAX) { ERROR (CHOLMOD_TOO_LARGE, "too many products for the product map") ; return FALSE ; }
+    const size_t np1 = npairs > 0 ? (size_t) npairs : 1 ;
+    int64_t *cp = cholmod_l_malloc (cnz + 1, sizeof (int64_t), Common) ;
+    int64_t *ia = cholmod_l_malloc (np1, sizeof (int64_t), Common) ;
+    int64_t *ib = cholmod_l_malloc (np1, sizeof (int64_t), Common) ;
+    int rm = CHOLMOD_HIP_OUT_OF_MEMORY ;
+    if (cp && ia && ib && cholmod_l_hip_aat_product_map (A, cp, ia, ib, Common) == npairs)
+        rm = cholmod_hip_set_product_map ((cholmod_hip_plan *) L->hip_plan, cp, ia, ib, (int64_t) cnz, (int64_t) annz) ;
+    if (cp) cholmod_l_free (cnz + 1, sizeof (int64_t), cp, Common) ;
+    if (ia) cholmod_l_free (np1, sizeof (int64_t), ia, Common) ;
+    if (ib) cholmod_l_free (np1, sizeof (int64_t), ib, Common) ;
+    L->hip_aat_valid = FALSE ;
+    if (rm != CHOLMOD_HIP_OK)
+    {
+        if (Common->status < CHOLMOD_OK) return FALSE ;       /* (out of host memory: reported already) */
+        return map_hip_status (rm, Common, "the product map could not be stored on the device") ;
+    }
+    L->hip_aat_hash = hash [0] ; L->hip_aat_hash2 = hash [1] ; L->hip_aat_nnz = annz ;
+    L->hip_aat_valid = TRUE ;
+    return TRUE ;
+}
+
 /* cholmod_l_factorize for values of A that live in device memory (cholmod.h).  The proof that the resident matrix and its
  * value map fit A is the pattern hash, taken BEFORE anything is enqueued here (the host path overlaps it with the upload;
  * there is no upload to hide it behind): a mismatch touches no device state. */
@@ -800,39 +841,7 @@ int cholmod_l_hip_factorize_values_device (cholmod_sparse *A, const double *Ax_d
         if (L->hip_apat_nnz != annz || L->hip_apat_hash != hash [0] || L->hip_apat_hash2 != hash [1])
         { ERROR (CHOLMOD_INVALID, "A does not have the pattern L was last factorized from") ; return FALSE ; }
     }
-    else if (!(L->hip_aat_valid && L->hip_aat_nnz == annz && L->hip_aat_hash == hash [0] && L->hip_aat_hash2 == hash [1]))
-    {
-        /* the resident matrix is tril (A*A'): its pattern from A's, against the record; then the lists of products */
-        cholmod_sparse *Cm = ssamd_aat (A, NULL, 0, TRUE, Common) ;
-        if (!Cm) return FALSE ;
-        uint64_t chash [2] ;
-        chash [0] = pattern_hash (Cm, &chash [1]) ;
-        const size_t cnz = (size_t) ((Int *) Cm->p) [Cm->ncol] ;
-        cholmod_l_free_sparse (&Cm, Common) ;
-        if (L->hip_apat_nnz != cnz || L->hip_apat_hash != chash [0] || L->hip_apat_hash2 != chash [1])
-        { ERROR (CHOLMOD_INVALID, "A*A' does not have the pattern L was last factorized from") ; return FALSE ; }
-        const int64_t npairs = cholmod_l_hip_aat_product_map (A, NULL, NULL, NULL, Common) ;
-        if (npairs < 0) return FALSE ;
-        if (npairs > INT32_MAX) { ERROR (CHOLMOD_TOO_LARGE, "too many products for the product map") ; return FALSE ; }
-        const size_t np1 = npairs > 0 ? (size_t) npairs : 1 ;
-        int64_t *cp = cholmod_l_malloc (cnz + 1, sizeof (int64_t), Common) ;
-        int64_t *ia = cholmod_l_malloc (np1, sizeof (int64_t), Common) ;
-        int64_t *ib = cholmod_l_malloc (np1, sizeof (int64_t), Common) ;
-        int rm = CHOLMOD_HIP_OUT_OF_MEMORY ;
-        if (cp && ia && ib && cholmod_l_hip_aat_product_map (A, cp, ia, ib, Common) == npairs)
-            rm = cholmod_hip_set_product_map (plan, cp, ia, ib, (int64_t) cnz, (int64_t) annz) ;
-        if (cp) cholmod_l_free (cnz + 1, sizeof (int64_t), cp, Common) ;
-        if (ia) cholmod_l_free (np1, sizeof (int64_t), ia, Common) ;
-        if (ib) cholmod_l_free (np1, sizeof (int64_t), ib, Common) ;
-        L->hip_aat_valid = FALSE ;
-        if (rm != CHOLMOD_HIP_OK)
-        {
-            if (Common->status < CHOLMOD_OK) return FALSE ;       /* (out of host memory: reported already) */
-            return map_hip_status (rm, Common, "the product map could not be stored on the device") ;
-        }
-        L->hip_aat_hash = hash [0] ; L->hip_aat_hash2 = hash [1] ; L->hip_aat_nnz = annz ;
-        L->hip_aat_valid = TRUE ;
-    }
+    else if (!ssamd_aat_product_map_ready (A, L, annz, hash, Common)) return FALSE ;
     int64_t minor = (int64_t) L->n ;
     const int rc = cholmod_hip_factorize_values_device (plan, Ax_dev, (int64_t) annz, beta ? beta [0] : 0.0,
         Common->quick_return_if_not_posdef, stream, &minor) ;
