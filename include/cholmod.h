@@ -261,7 +261,8 @@ typedef struct cholmod_factor_struct
                                  * complex px; CHOLMOD_HIP_CX_STORAGE) */
     void *bset_work ;           /* cholmod_l_solve2 with Bset: column -> supernode, flags (2n + 1 integers, built by the first call) */
     int hip_plan_ahead ;        /* != 0: hip_plan was built inside cholmod_l_analyze and no factorization has used it yet (plan flags + 1) */
-    int hip_perm_set ;          /* hip_plan holds L->Perm (cholmod_l_hip_solve_device hands it over on first use) */
+    int hip_perm_set ;          /* hip_plan holds L->Perm (cholmod_l_hip_solve_device hands it over on first use); on the twin
+                                 * of a complex factor: the expanded permutation 2 Perm [k], 2 Perm [k] + 1 of that factor */
     /* cholmod_l_hip_factorize_values_device with an unsymmetric A (stype 0): hip_apat_hash is then the hash of tril (A*A')'s
      * pattern; once A's product map is on the plan these hold the hash of A's OWN pattern, all a later call pays for */
     uint64_t hip_aat_hash, hip_aat_hash2 ;
@@ -415,6 +416,25 @@ int cholmod_l_hip_solve_device (int sys, cholmod_factor *L, const double *B_dev,
 int cholmod_l_hip_residual_device (cholmod_factor *L, const double *X_dev, size_t ldx, const double *B_dev, size_t ldb,
     double *R_dev, size_t ldr, size_t nrhs, double *Rnorm_dev, void *stream, cholmod_common *Common) ;
 int cholmod_l_hip_refine_device (cholmod_factor *L, const double *B_dev, size_t ldb, double *X_dev, size_t ldx,
+    size_t nrhs, int steps, double *Rnorm_dev, void *stream, cholmod_common *Common) ;
+/* The same three for a complex factor: L is the complex supernodal factor of a Hermitian A (computed from complex or
+ * zomplex input) whose last factorization ran on the engine, one rank.  B_dev, X_dev and R_dev hold interleaved complex
+ * doubles (re, im), n-by-nrhs, column-major, leading dimensions in COMPLEX elements; rows n .. ld-1 are neither read nor
+ * written; B_dev == X_dev with equal ld is legal, R_dev may be B_dev and must not be X_dev.  sys as in cholmod_l_solve:
+ * CHOLMOD_Lt and CHOLMOD_DLt mean L^H, D is the identity.  Rnorm_dev [k] (nrhs real doubles, NULL allowed) is what the
+ * engine forms on the real twin of L: max_i max (|re R (i,k)|, |im R (i,k)|), not the complex modulus.  Stream ordering,
+ * the bit-identical residual of two calls and "nothing allocated after the first call" are those of the real entry points
+ * above; the solves run on the twin's plan (8 or more right-hand sides in panels of 16 on v_mfma_f64_16x16x4, L read once
+ * per panel in its complex storage).
+ * FALSE, before any device call: with CHOLMOD_INVALID for a NULL pointer, sys out of range, ld < n, steps < 0,
+ * R_dev == X_dev, a real, pattern or simplicial L (a real L has the entry points above), the GPU switched off, several
+ * ranks, or an L whose factor is not on the device (there is never a host fallback); with CHOLMOD_NOT_INSTALLED for a
+ * zomplex L.  nrhs == 0 or n == 0 is a success that touches nothing. */
+int cholmod_l_hip_solve_device_complex (int sys, cholmod_factor *L, const void *B_dev, size_t ldb, void *X_dev, size_t ldx,
+    size_t nrhs, void *stream, cholmod_common *Common) ;
+int cholmod_l_hip_residual_device_complex (cholmod_factor *L, const void *X_dev, size_t ldx, const void *B_dev, size_t ldb,
+    void *R_dev, size_t ldr, size_t nrhs, double *Rnorm_dev, void *stream, cholmod_common *Common) ;
+int cholmod_l_hip_refine_device_complex (cholmod_factor *L, const void *B_dev, size_t ldb, void *X_dev, size_t ldx,
     size_t nrhs, int steps, double *Rnorm_dev, void *stream, cholmod_common *Common) ;
 /* The selected inverse (the sparse inverse subset; the reference ships it as MATLAB_Tools/sparseinv): the entries of
  * Z = (A + beta I)^-1 on the pattern of L -- hence on the pattern of A -- for the A and beta L was last factorized from ON

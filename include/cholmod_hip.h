@@ -346,9 +346,14 @@ int cholmod_hip_set_perm (cholmod_hip_plan *plan, const int64_t *Perm) ;
  * run on v_mfma_f64_16x16x4.
  * Needs a numeric factor on the device (several ranks: after the gather, as above) and,
  * for perm_in / perm_out, the permutation.  CHOLMOD_HIP_INVALID for a host-only plan,
- * NULL pointers, ld < n, nrhs < 0, a missing permutation, and for the plans of complex
- * factors (CHOLMOD_HIP_PHI_TWIN, CHOLMOD_HIP_CX_STORAGE); nrhs == 0 is a success that
- * touches nothing.  stats [24] is read from the solve's two events when the statistics
+ * NULL pointers, ld < n, nrhs < 0 and a missing permutation; nrhs == 0 is a success that
+ * touches nothing.
+ * The plan of a complex factor is served too.  Its n, ld and permutation are the twin's: a
+ * column is 2 n_complex doubles, the interleaved (re, im) entries, and the permutation is
+ * the expanded one (2 Perm [k], 2 Perm [k] + 1).  The full twin (CHOLMOD_HIP_PHI_TWIN alone)
+ * is an ordinary real factor and runs the real kernels; in complex storage
+ * (CHOLMOD_HIP_CX_STORAGE) both kernel families read the interleaved complex panels, half
+ * the twin's bytes, and rebuild the odd twin columns on the way in.  stats [24] is read from the solve's two events when the statistics
  * are asked for, which may wait for the solve. */
 int cholmod_hip_solve_device (cholmod_hip_plan *plan, int which, int perm_in, int perm_out,
     const double *dB, int64_t ldb, double *dX, int64_t ldx, int64_t nrhs, void *stream) ;
@@ -367,14 +372,18 @@ int cholmod_hip_solve_device (cholmod_hip_plan *plan, int which, int perm_in, in
  * call is ordered on `stream` exactly as cholmod_hip_solve_device is (not during capture).
  * CHOLMOD_HIP_INVALID, before any device call: NULL plan or pointers, a host-only plan, a plan of several ranks, ld < n,
  * nrhs < 0, dR == dX, perm without a stored permutation, no resident S (a factor brought in by cholmod_hip_upload_factor
- * only), the plans of complex factors (CHOLMOD_HIP_PHI_TWIN, CHOLMOD_HIP_CX_STORAGE). */
+ * only).
+ * The plan of a complex factor (CHOLMOD_HIP_PHI_TWIN, CHOLMOD_HIP_CX_STORAGE) is served like a real one: its resident S is
+ * the real symmetric phi (S) of the twin, X, B and R are the interleaved complex columns (2 n_complex doubles each, ld in
+ * doubles), and dRnorm [k] = max_i max (|re R (i,k)|, |im R (i,k)|). */
 int cholmod_hip_residual_device (cholmod_hip_plan *plan, int perm, const double *dX, int64_t ldx, const double *dB,
     int64_t ldb, double *dR, int64_t ldr, int64_t nrhs, double *dRnorm, void *stream) ;
 
 /* `steps` rounds of  X += (LL')^-1 (B - (A + beta I) X)  in place on dX (perm as above), then the residual norms of
  * the final X into dRnorm (NULL allowed).  steps == 0: X untouched, norms only.  The iteration stays in the factor's
  * ordering: B and X pass through Perm once on the way in, X once on the way out.  Needs what the residual needs and,
- * for steps > 0, the numeric factor as cholmod_hip_solve_device does; steps < 0 is CHOLMOD_HIP_INVALID. */
+ * for steps > 0, the numeric factor as cholmod_hip_solve_device does; steps < 0 is CHOLMOD_HIP_INVALID.  The plans of
+ * complex factors as for the residual and the solve. */
 int cholmod_hip_refine_device (cholmod_hip_plan *plan, int perm, const double *dB, int64_t ldb, double *dX, int64_t ldx,
     int64_t nrhs, int steps, double *dRnorm, void *stream) ;
 

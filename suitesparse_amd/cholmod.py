@@ -148,6 +148,7 @@ API_SYMBOLS = [
     "cholmod_l_factor_to_host", "cholmod_l_hip_stats", "cholmod_l_refactorize_resident",
     "cholmod_l_gather_factor", "cholmod_l_hip_prepare", "cholmod_l_hip_front_reach",
     "cholmod_l_hip_solve_device", "cholmod_l_hip_residual_device", "cholmod_l_hip_refine_device",
+    "cholmod_l_hip_solve_device_complex", "cholmod_l_hip_residual_device_complex", "cholmod_l_hip_refine_device_complex",
     "cholmod_l_hip_factorize_values_device", "cholmod_l_hip_aat_product_map",
     "cholmod_l_hip_selinv_device", "cholmod_l_hip_selinv_to_host",
     "cholmod_l_hip_values_grad_device", "cholmod_l_hip_logdet_device",
@@ -303,6 +304,9 @@ def lib(hooks=None):
     sig("cholmod_hip_refine_device", C.c_int, [vp, C.c_int, vp, i64, vp, i64, i64, C.c_int, vp, vp])
     sig("cholmod_l_hip_residual_device", C.c_int, [fc, vp, sz, vp, sz, vp, sz, sz, vp, vp, cm])
     sig("cholmod_l_hip_refine_device", C.c_int, [fc, vp, sz, vp, sz, sz, C.c_int, vp, vp, cm])
+    sig("cholmod_l_hip_solve_device_complex", C.c_int, [C.c_int, fc, vp, sz, vp, sz, sz, vp, cm])
+    sig("cholmod_l_hip_residual_device_complex", C.c_int, [fc, vp, sz, vp, sz, vp, sz, sz, vp, vp, cm])
+    sig("cholmod_l_hip_refine_device_complex", C.c_int, [fc, vp, sz, vp, sz, sz, C.c_int, vp, vp, cm])
     sig("cholmod_hip_factorize_values_device", C.c_int, [vp, vp, i64, dbl, C.c_int, vp, C.POINTER(i64)])
     sig("cholmod_hip_set_product_map", C.c_int, [vp, vp, vp, vp, i64, i64])
     sig("cholmod_hip_download_matrix_values", C.c_int, [vp, vp])
@@ -527,13 +531,21 @@ class Session:
         return out
 
     @staticmethod
-    def _device_layout(what, n, t, like=None):
-        """(leading dimension, right-hand sides) of the column-major n-by-nrhs matrix the rows of the device tensor t
-        are: torch.float64, shape (nrhs, n) or (n,), unit stride along a row, any row stride >= n; `like`: a tensor
-        whose shape and device t must share."""
+    def _device_dtype(Lf):
+        """(dtype of the device tensors that go with the factor Lf, suffix of its entry points): torch.complex128 and the
+        `_complex` entry points for a complex factor, torch.float64 and the real ones for every other."""
         import torch
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64):
-            raise (TypeError if like is None else ValueError)(f"{what} must be a torch.float64 tensor on the device")
+        return (torch.complex128, "_complex") if Lf.contents.xtype == COMPLEX else (torch.float64, "")
+
+    @staticmethod
+    def _device_layout(what, n, t, like=None, dtype=None):
+        """(leading dimension, right-hand sides) of the column-major n-by-nrhs matrix the rows of the device tensor t
+        are: torch.float64 (or `dtype`), shape (nrhs, n) or (n,), unit stride along a row, any row stride >= n, both in
+        elements of the tensor; `like`: a tensor whose shape and device t must share."""
+        import torch
+        dtype = dtype or torch.float64
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
+            raise (TypeError if like is None else ValueError)(f"{what} must be a {dtype} tensor on the device")
         if t.dim() not in (1, 2) or t.shape[-1] != n:
             raise ValueError(f"{what} must have shape (nrhs, {n}) or ({n},)")
         if like is not None and (t.shape != like.shape or t.device != like.device):
@@ -552,18 +564,21 @@ class Session:
         and any row stride >= n.  Returns a device tensor of the same shape, or writes into `out` (`out is B`: in
         place).  The solve is enqueued on torch's current stream; nothing is copied to the host and the host does not
         wait for it.  torch must have been imported before the library was loaded (before the first Session), so that
-        the two share one HIP runtime."""
+        the two share one HIP runtime.  A complex factor takes torch.complex128 tensors of the same shapes (strides in
+        complex elements) and goes through cholmod_l_hip_solve_device_complex; a dtype that does not match the factor
+        is a TypeError."""
         import torch
         n = int(Lf.contents.n)
-        ldb, nrhs = self._device_layout("solve_device: B", n, B)
+        dt, sfx = self._device_dtype(Lf)
+        ldb, nrhs = self._device_layout("solve_device: B", n, B, dtype=dt)
         if out is None:
-            out = torch.empty(B.shape, dtype=torch.float64, device=B.device)
-        ldx, _ = self._device_layout("solve_device: out", n, out, like=B)
+            out = torch.empty(B.shape, dtype=dt, device=B.device)
+        ldx, _ = self._device_layout("solve_device: out", n, out, like=B, dtype=dt)
         stream = torch.cuda.current_stream(B.device).cuda_stream
-        ok = self.L.cholmod_l_hip_solve_device(sys, Lf, B.data_ptr() or 1, ldb, out.data_ptr() or 1, ldx, nrhs,
-                                               stream, C.byref(self.cm))
+        fn = getattr(self.L, "cholmod_l_hip_solve_device" + sfx)
+        ok = fn(sys, Lf, B.data_ptr() or 1, ldb, out.data_ptr() or 1, ldx, nrhs, stream, C.byref(self.cm))
         if not ok:
-            raise RuntimeError(f"cholmod_l_hip_solve_device failed, status {self.cm.status}")
+            raise RuntimeError(f"cholmod_l_hip_solve_device{sfx} failed, status {self.cm.status}")
         return out
 
     def residual_device(self, Lf, X, B, out=None, norms=False):
@@ -571,38 +586,42 @@ class Session:
         (plus beta I).  X, B: device tensors as for `solve_device`, of one shape.  Returns R as a new tensor or in `out`
         (`out is B`: in place; never X); with norms=True, (R, norms): norms a device tensor of length nrhs holding
         max |R| of every right-hand side.  Enqueued on torch's current stream; two calls on the same inputs give the same
-        bits."""
+        bits.  A complex factor: torch.complex128 tensors (cholmod_l_hip_residual_device_complex); norms stays
+        torch.float64 and holds the largest |re| or |im| of every right-hand side of R."""
         import torch
         n = int(Lf.contents.n)
-        ldx, nrhs = self._device_layout("residual_device: X", n, X)
-        ldb, _ = self._device_layout("residual_device: B", n, B, like=X)
+        dt, sfx = self._device_dtype(Lf)
+        ldx, nrhs = self._device_layout("residual_device: X", n, X, dtype=dt)
+        ldb, _ = self._device_layout("residual_device: B", n, B, like=X, dtype=dt)
         if out is None:
-            out = torch.empty(X.shape, dtype=torch.float64, device=X.device)
-        ldr, _ = self._device_layout("residual_device: out", n, out, like=X)
+            out = torch.empty(X.shape, dtype=dt, device=X.device)
+        ldr, _ = self._device_layout("residual_device: out", n, out, like=X, dtype=dt)
         nrm = torch.empty(nrhs, dtype=torch.float64, device=X.device) if norms else None
         stream = torch.cuda.current_stream(X.device).cuda_stream
         # (empty tensors have no address: distinct stand-ins, R must not be X)
-        ok = self.L.cholmod_l_hip_residual_device(Lf, X.data_ptr() or 1, ldx, B.data_ptr() or 2, ldb, out.data_ptr() or 3,
-                                                  ldr, nrhs, nrm.data_ptr() if norms and nrhs else None, stream,
-                                                  C.byref(self.cm))
+        fn = getattr(self.L, "cholmod_l_hip_residual_device" + sfx)
+        ok = fn(Lf, X.data_ptr() or 1, ldx, B.data_ptr() or 2, ldb, out.data_ptr() or 3, ldr, nrhs,
+                nrm.data_ptr() if norms and nrhs else None, stream, C.byref(self.cm))
         if not ok:
-            raise RuntimeError(f"cholmod_l_hip_residual_device failed, status {self.cm.status}")
+            raise RuntimeError(f"cholmod_l_hip_residual_device{sfx} failed, status {self.cm.status}")
         return (out, nrm) if norms else out
 
     def refine_device(self, Lf, B, X, steps=1, norms=False):
         """cholmod_l_hip_refine_device: `steps` rounds of X += A^-1 (B - A X) with the factor Lf, in place on the device
         tensor X, which is returned; with norms=True, (X, norms): the residual norms of the final X (steps=0: X is left
-        alone and only its norms are formed).  Tensors and stream as for `residual_device`."""
+        alone and only its norms are formed).  Tensors, stream and complex factors as for `residual_device`."""
         import torch
         n = int(Lf.contents.n)
-        ldb, nrhs = self._device_layout("refine_device: B", n, B)
-        ldx, _ = self._device_layout("refine_device: X", n, X, like=B)
+        dt, sfx = self._device_dtype(Lf)
+        ldb, nrhs = self._device_layout("refine_device: B", n, B, dtype=dt)
+        ldx, _ = self._device_layout("refine_device: X", n, X, like=B, dtype=dt)
         nrm = torch.empty(nrhs, dtype=torch.float64, device=X.device) if norms else None
         stream = torch.cuda.current_stream(X.device).cuda_stream
-        ok = self.L.cholmod_l_hip_refine_device(Lf, B.data_ptr() or 2, ldb, X.data_ptr() or 1, ldx, nrhs, int(steps),
-                                                nrm.data_ptr() if norms and nrhs else None, stream, C.byref(self.cm))
+        fn = getattr(self.L, "cholmod_l_hip_refine_device" + sfx)
+        ok = fn(Lf, B.data_ptr() or 2, ldb, X.data_ptr() or 1, ldx, nrhs, int(steps),
+                nrm.data_ptr() if norms and nrhs else None, stream, C.byref(self.cm))
         if not ok:
-            raise RuntimeError(f"cholmod_l_hip_refine_device failed, status {self.cm.status}")
+            raise RuntimeError(f"cholmod_l_hip_refine_device{sfx} failed, status {self.cm.status}")
         return (X, nrm) if norms else X
 
     def selinv_device(self, A, Lf, values=True, diag=True):

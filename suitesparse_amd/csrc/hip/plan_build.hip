@@ -536,8 +536,13 @@ struct PlanBuilder
     }
 
     // ---- solve tasks (all supernodes: after cholmod_hip_gather_factor every rank holds L) -------------------------------------
-    void build_solve_tasks ()
+    // A twin (complex factor) has every bound even: nscol and nsrow of a front, hence jb (a multiple of SOLVE_SB) and w of
+    // a block.  The solve kernels in complex storage rely on it -- ldcx reads row r ^ 1 of an in-range row r and column
+    // c >> 1 of the stored panel -- and do not check it themselves: an odd bound in such a plan is refused here.
+    int build_solve_tasks ()
     {
+        const bool cx = (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;
+        auto odd = [] (i64 a, i64 b) { return ((a | b) & 1) != 0 ; } ;
         P->sv_tasks.clear () ; P->sv_ptr.assign (nlev + 1, 0) ; P->sv_big.assign (nlev, {}) ;
         for (int l = 0 ; l < nlev ; l++)
         {
@@ -545,6 +550,7 @@ struct PlanBuilder
             {
                 i32 sid = P->lvl_list [q] ;
                 const FrontD &f = P->fr [sid] ;
+                if (cx && odd (f.nscol, f.nsrow)) return CHOLMOD_HIP_INVALID ;
                 // one workgroup streams ~50-100 GB/s: anything above 512 KB of L gets the multi-workgroup block walk
                 if (f.nscol > SOLVE_BIG_COLS || (i64) f.nsrow * f.nscol > ((i64) 1 << 16)) P->sv_big [l].push_back (sid) ;
                 else P->sv_tasks.push_back (SolveTask {sid, 0, f.nscol, 1}) ;
@@ -578,6 +584,7 @@ struct PlanBuilder
                     int jb = b * SOLVE_SB ;
                     if (jb >= f.nscol) continue ;
                     int w = std::min (SOLVE_SB, f.nscol - jb) ;
+                    if (cx && odd (jb, w)) return CHOLMOD_HIP_INVALID ;
                     int rest = f.nsrow - (jb + w) ;
                     P->sb_tasks.push_back (SolveBlk {sid, jb, w, Lb.grid, (i32) (P->inv_first [sid] + jb / SOLVE_IB), Lb.ntasks}) ;
                     // workgroups: 256-row chunks below the block x 64-column sub-blocks
@@ -588,6 +595,7 @@ struct PlanBuilder
             }
             P->sb_lvl_ptr [l+1] = (i32) P->sb_launch.size () ;
         }
+        return CHOLMOD_HIP_OK ;
     }
 
     // ---- windows of the distributed fronts: at the tail of the rank's array, alive for the front's batch only (the region is
@@ -841,7 +849,8 @@ struct PlanBuilder
         layout_local_factor () ;
         build_child_lists () ;
         choose_batches () ;
-        build_solve_tasks () ;
+        rc = build_solve_tasks () ;
+        if (rc != CHOLMOD_HIP_OK) return rc ;
         layout_windows () ;
         schedule_batches () ;
         // (known from the plan alone: a host-only plan reports it too)

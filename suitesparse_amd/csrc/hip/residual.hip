@@ -53,11 +53,11 @@ static int build_index (cholmod_hip_plan *P)
     return CHOLMOD_HIP_OK ;
 }
 
-// what both entry points refuse, before any device call
+// what both entry points refuse, before any device call.  (The twin of a complex factor is served like a real one: its
+// resident phi (S) is a real symmetric matrix, n, ld and the permutation are the twin's.)
 static bool bad_plan (const cholmod_hip_plan *P, int perm)
 {
     if (!P || P->host_only || P->world > 1) return true ;
-    if (P->flags & (CHOLMOD_HIP_CX_STORAGE | CHOLMOD_HIP_PHI_TWIN)) return true ;       // real factors only
     if (perm && !P->d_perm) return true ;                                               // cholmod_hip_set_perm first
     return !P->d_Sp ;                                                                   // no resident matrix (it may have no entry)
 }
@@ -114,8 +114,9 @@ struct Group {
     // W = (LL')^-1 W, then X += W
     void correct (const FrontD *frw, const double *Lw, double *W, double *X) const
     {
-        if (columns) sd_sweeps_columns (P, 0, frw, Lw, st, W, P->n, w) ;
-        else sd_sweeps_panel (P, 0, frw, Lw, st, W) ;
+        const bool cxs = (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;
+        if (columns) sd_sweeps_columns (P, 0, frw, Lw, cxs, st, W, P->n, w) ;
+        else sd_sweeps_panel (P, 0, frw, Lw, cxs, st, W) ;
         hipLaunchKernelGGL (k_rs_add, dim3 ((unsigned) ((count () + 255) / 256)), dim3 (256), 0, st, count (), X, (const double *) W) ;
     }
 } ;
@@ -181,7 +182,7 @@ int cholmod_hip_refine_device (cholmod_hip_plan *P, int perm, const double *dB, 
     RS_TRY (rs_ensure (P, steps > 0, columns)) ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
     RS_TRY (enter (P, user, dRnorm, nrhs)) ;
-    if (steps > 0) refresh_inverses (P, frw, Lw, false) ;
+    if (steps > 0) refresh_inverses (P, frw, Lw, (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0) ;
     const i64 *pm = perm ? P->d_perm : nullptr ;
     double *W = P->d_sd_W, *Xp = P->d_rs_X, *Bp = P->d_rs_B ;
     const i64 step = columns ? nrhs : SD_NP ;

@@ -51,37 +51,37 @@ struct ColumnKernels {
 } ;
 
 // ... and with the 16-wide ones: a panel of up to 16 right-hand sides, in place on W [n][16], L read once.  They update W
-// as they go, so there is nothing to commit.
+// as they go, so there is nothing to commit.  cxs: L is a complex factor in its own storage (W is the twin's either way).
 struct PanelKernels {
     const cholmod_hip_plan *P ; const FrontD *frw ; const double *Lw ; hipStream_t st ;
-    double *W ;
+    double *W ; bool cxs ;
     void lsolve (const SolveTask *t, int nf) const
     {
-        hipLaunchKernelGGL (k_sd_lsolve, dim3 (nf), dim3 (256), 0, st, t, frw, P->d_Ls, Lw, W) ;
+        CXS_LAUNCH (k_sd_lsolve, dim3 (nf), dim3 (256), 0, st, t, frw, P->d_Ls, Lw, W) ;
     }
     void fwd_diag (const SbLaunch &B) const
     {
-        hipLaunchKernelGGL (k_sd_fwd_diag, dim3 (B.ntasks), dim3 (256), 0, st, P->d_sb_tasks + B.first, frw, Lw, P->d_winv, W) ;
+        CXS_LAUNCH (k_sd_fwd_diag, dim3 (B.ntasks), dim3 (256), 0, st, P->d_sb_tasks + B.first, frw, Lw, P->d_winv, W) ;
     }
     void fwd_apply (const SbLaunch &B) const
     {
-        hipLaunchKernelGGL (k_sd_fwd_apply, dim3 (B.grid), dim3 (256), 0, st,
+        CXS_LAUNCH (k_sd_fwd_apply, dim3 (B.grid), dim3 (256), 0, st,
             P->d_sb_tasks + B.first, (int) B.ntasks, frw, P->d_Ls, Lw, W) ;
     }
     void commit (const SbLaunch &) const {}
     void bwd_apply (const SbLaunch &B) const
     {
-        hipLaunchKernelGGL (k_sd_bwd_apply, dim3 (B.grid), dim3 (256), 0, st,
+        CXS_LAUNCH (k_sd_bwd_apply, dim3 (B.grid), dim3 (256), 0, st,
             P->d_sb_tasks + B.first, (int) B.ntasks, frw, P->d_Ls, Lw, W, P->d_sd_acc) ;
     }
     void bwd_diag (const SbLaunch &B) const
     {
-        hipLaunchKernelGGL (k_sd_bwd_diag, dim3 (B.ntasks), dim3 (256), 0, st,
+        CXS_LAUNCH (k_sd_bwd_diag, dim3 (B.ntasks), dim3 (256), 0, st,
             P->d_sb_tasks + B.first, frw, Lw, P->d_winv, W, P->d_sd_acc) ;
     }
     void ltsolve (const SolveTask *t, int nf) const
     {
-        hipLaunchKernelGGL (k_sd_ltsolve, dim3 (nf), dim3 (256), 0, st, t, frw, P->d_Ls, Lw, W) ;
+        CXS_LAUNCH (k_sd_ltsolve, dim3 (nf), dim3 (256), 0, st, t, frw, P->d_Ls, Lw, W) ;
     }
 } ;
 
@@ -278,14 +278,14 @@ void sd_unpack (hipStream_t st, i64 n, const i64 *perm, const double *W, int pw,
     hipLaunchKernelGGL (k_sd_unpack, dim3 ((unsigned) ((n + 255) / 256)), dim3 (256), 0, st, n, perm, W, pw, X, ldx) ;
 }
 
-void sd_sweeps_columns (const cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, hipStream_t st, double *x, i64 ldx, int nrhs)
+void sd_sweeps_columns (const cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, bool cxs, hipStream_t st, double *x, i64 ldx, int nrhs)
 {
-    solve_sweeps (P, which, ColumnKernels {P, frw, Lw, st, x, ldx, nrhs, false}) ;
+    solve_sweeps (P, which, ColumnKernels {P, frw, Lw, st, x, ldx, nrhs, cxs}) ;
 }
 
-void sd_sweeps_panel (const cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, hipStream_t st, double *W)
+void sd_sweeps_panel (const cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, bool cxs, hipStream_t st, double *W)
 {
-    solve_sweeps (P, which, PanelKernels {P, frw, Lw, st, W}) ;
+    solve_sweeps (P, which, PanelKernels {P, frw, Lw, st, W, cxs}) ;
 }
 
 } // namespace sship
@@ -295,7 +295,6 @@ int cholmod_hip_solve_device (cholmod_hip_plan *P, int which, int perm_in, int p
 {
     if (!P || P->host_only || !dB || !dX || nrhs < 0 || ldb < P->n || ldx < P->n || which < 0 || which > 3)
         return CHOLMOD_HIP_INVALID ;
-    if (P->flags & (CHOLMOD_HIP_CX_STORAGE | CHOLMOD_HIP_PHI_TWIN)) return CHOLMOD_HIP_INVALID ;     // real factors only
     if ((perm_in || perm_out) && !P->d_perm) return CHOLMOD_HIP_INVALID ;       // cholmod_hip_set_perm first
     const i64 n = P->n ;
     if (nrhs == 0 || n == 0) return CHOLMOD_HIP_OK ;
@@ -307,13 +306,16 @@ int cholmod_hip_solve_device (cholmod_hip_plan *P, int which, int perm_in, int p
         frw = whole_fronts (P) ;
         if (!Lw || !frw) return CHOLMOD_HIP_INVALID ;  // several ranks: cholmod_hip_gather_factor first
     }
+    // a complex factor: the full twin (CHOLMOD_HIP_PHI_TWIN alone) is an ordinary real factor; in its own storage the
+    // kernels rebuild the odd twin columns as they read (n, ld and the permutation are the twin's either way)
+    const bool cxs = (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;
     const bool columns = nrhs < SD_BLOCK_MIN_NRHS ;
     { int rc = sd_ensure (P, which != 3, columns) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
     // the engine stream takes its place in the caller's order: behind what the caller has enqueued ...
     HIPCHK (hipEventRecord (P->sd_ev_in, user)) ;
     HIPCHK (hipStreamWaitEvent (st, P->sd_ev_in, 0)) ;
-    if (which != 3) refresh_inverses (P, frw, Lw, false) ;
+    if (which != 3) refresh_inverses (P, frw, Lw, cxs) ;
     HIPCHK (hipEventRecord (P->sd_ev0, st)) ;
     const i64 *pin = perm_in ? P->d_perm : nullptr, *pout = perm_out ? P->d_perm : nullptr ;
     const unsigned nblk = (unsigned) ((n + 255) / 256) ;
@@ -322,14 +324,14 @@ int cholmod_hip_solve_device (cholmod_hip_plan *P, int which, int perm_in, int p
     {
         // directly on the permuted columns, W as [nrhs][n]
         { int rc = sd_move_columns (st, n, nrhs, pin, 0, dB, ldb, W, n) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
-        if (which != 3) solve_sweeps (P, which, ColumnKernels {P, frw, Lw, st, W, n, (int) nrhs, false}) ;
+        if (which != 3) solve_sweeps (P, which, ColumnKernels {P, frw, Lw, st, W, n, (int) nrhs, cxs}) ;
         { int rc = sd_move_columns (st, n, nrhs, pout, 1, W, n, dX, ldx) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
     }
     else for (i64 r0 = 0 ; r0 < nrhs ; r0 += SD_NP)
     {
         const int pw = (int) std::min<i64> (SD_NP, nrhs - r0) ;
         hipLaunchKernelGGL (k_sd_pack, dim3 (nblk), dim3 (256), 0, st, n, pin, dB + r0 * ldb, (i64) ldb, pw, W) ;
-        if (which != 3) solve_sweeps (P, which, PanelKernels {P, frw, Lw, st, W}) ;
+        if (which != 3) solve_sweeps (P, which, PanelKernels {P, frw, Lw, st, W, cxs}) ;
         hipLaunchKernelGGL (k_sd_unpack, dim3 (nblk), dim3 (256), 0, st, n, pout, (const double *) W, pw, dX + r0 * ldx, (i64) ldx) ;
     }
     HIPCHK (hipGetLastError ()) ;

@@ -28,8 +28,8 @@ int sd_move_columns (hipStream_t st, i64 n, i64 nrhs, const i64 *perm, int inver
 void sd_pack (hipStream_t st, i64 n, const i64 *perm, const double *B, i64 ldb, int pw, double *W) ;
 void sd_unpack (hipStream_t st, i64 n, const i64 *perm, const double *W, int pw, double *X, i64 ldx) ;
 // solve_sweeps (which: 0 = L then L', 1 = L, 2 = L') with the one-column kernels on x [nrhs][ldx], with the 16-wide
-// ones on W [n][16]; real factors
-void sd_sweeps_columns (const cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, hipStream_t st, double *x, i64 ldx, int nrhs) ;
-void sd_sweeps_panel (const cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, hipStream_t st, double *W) ;
+// ones on W [n][16]; cxs: Lw is a complex factor in its own storage (CHOLMOD_HIP_CX_STORAGE)
+void sd_sweeps_columns (const cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, bool cxs, hipStream_t st, double *x, i64 ldx, int nrhs) ;
+void sd_sweeps_panel (const cholmod_hip_plan *P, int which, const FrontD *frw, const double *Lw, bool cxs, hipStream_t st, double *W) ;
 
 } // namespace sship

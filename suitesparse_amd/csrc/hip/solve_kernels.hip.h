@@ -600,14 +600,21 @@ __global__ void k_perm (i64 n, const i64 *perm, const double *src, double *dst,
 //
 // The schedule is the plan's: the whole-supernode tasks of a level (SolveTask, one workgroup each) and the
 // 256-column blocks of the big supernodes (SolveBlk, the launches of sb_launch) with their explicit 64 x 64
-// inverses (k_diag_inv64).  Real factors only.
+// inverses (k_diag_inv64).
+//
+// CX = a complex factor in its own storage (device_util.hip.h): every read of L goes through ldcx<CX>, every block
+// base is formed with colx<CX> (twin column c lives at column c >> 1 of the nsrow-leading-dimension panel), and the
+// <false> forms are the real kernels unchanged.  ldcx touches row r ^ 1 of an in-range row r: every row and column
+// bound of a twin is even (plan_build.hip checks it where the task lists are built), so the partner row is in range.
+// W, the accumulators, the explicit inverses (full real 64 x 64 blocks) and the schedule are the twin's: real.
 #define SD_NP 16        /* right-hand sides per panel */
 
 __device__ __forceinline__ d4 sd_zero () { d4 z = {0.0, 0.0, 0.0, 0.0} ; return z ; }
 
 // acc (rows i0 .. i0+15, 16 right-hand sides) += M [i0 .., 0 .. K) * Xs [0 .. K)[.]
 // M: column-major, leading dimension ld (16 consecutive rows of a column per lane group: coalesced), rows >= ilim
-// read as zero; Xs: LDS, [K][16].
+// read as zero; Xs: LDS, [K][16].  CX: M addresses an even row and an even column of the twin, i0, ilim and K are even.
+template <bool CX>
 __device__ __forceinline__ d4 sd_mul_nx (const double *M, int ld, int i0, int ilim, int K, const double *Xs,
     d4 acc, int lr, int lk)
 {
@@ -618,7 +625,7 @@ __device__ __forceinline__ d4 sd_mul_nx (const double *M, int ld, int i0, int il
     {
         const int k = k0 + lk ;
         const bool ok = k < K ;
-        const double a = (rok && ok) ? Mi [(i64) k * ld] : 0.0 ;
+        const double a = (rok && ok) ? (CX ? ldcx<CX> (M, i, k, ld) : Mi [(i64) k * ld]) : 0.0 ;
         const double b = ok ? Xs [k * SD_NP + lr] : 0.0 ;
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64 (a, b, acc, 0, 0, 0) ;
     }
@@ -628,8 +635,10 @@ __device__ __forceinline__ d4 sd_mul_nx (const double *M, int ld, int i0, int il
 // acc (columns j0 .. j0+15 of M, 16 right-hand sides) += sum over rows i = ia, ia + 1, .. (16 at a time, then
 // istep further on) below ib of M [i, j0 ..]' y (i)[.]
 // A lane reads four consecutive rows of its column (lk-th quarter of the 16): a lane group covers 128 contiguous
-// bytes of each of its 16 columns, and the four values feed four k-steps.  Columns >= jlim read as zero.
-template <class YF>
+// bytes of each of its 16 columns, and the four values feed four k-steps.  Columns >= jlim read as zero.  CX: M
+// addresses an even row and an even column of the twin, ia, ib and jlim are even (a lane of an odd column reads its
+// four rows pairwise swapped: the same 32 bytes).
+template <bool CX, class YF>
 __device__ __forceinline__ d4 sd_mul_ty (const double *M, int ld, int j0, int jlim, int ia, int ib, int istep,
     YF y, d4 acc, int lr, int lk)
 {
@@ -644,7 +653,7 @@ __device__ __forceinline__ d4 sd_mul_ty (const double *M, int ld, int j0, int jl
         {
             const int i = ibase + 4 * lk + s ;
             const bool ok = i < ib ;
-            a [s] = (ok && cok) ? Mc [i] : 0.0 ;
+            a [s] = (ok && cok) ? (CX ? ldcx<CX> (M, i, j, ld) : Mc [i]) : 0.0 ;
             b [s] = ok ? y (i, lr) : 0.0 ;
         }
 #pragma unroll
@@ -689,14 +698,16 @@ __global__ void __launch_bounds__(256) k_sd_unpack (i64 n, const i64 *perm, cons
 
 // ---- whole supernodes (at most 256 columns, one workgroup each) ----------------------------------------------------
 // the 16 x 16 diagonal block at column jb into LDS, identity-padded past the supernode's last column
+template <bool CX>
 __device__ __forceinline__ void sd_stage_diag (const double *L, int nsrow, int jb, int nb, double *Dl, int tid)
 {
     const int i = tid & 15, j = tid >> 4 ;
-    Dl [i * 17 + j] = (i < nb && j < nb && j <= i) ? L [jb + i + (i64) (jb + j) * nsrow] : (i == j ? 1.0 : 0.0) ;
+    Dl [i * 17 + j] = (i < nb && j < nb && j <= i) ? ldcx<CX> (L, jb + i, jb + j, nsrow) : (i == j ? 1.0 : 0.0) ;
 }
 
 // forward: x1 = L1 \ x1 by 16-column blocks (substitution on 16 right-hand sides at once, one lane each, then the
 // rows below inside the supernode as tiles), W [Ls2] -= L2 x1 as tiles (siblings share ancestor rows: atomic)
+template <bool CX>
 __global__ void __launch_bounds__(256) k_sd_lsolve (const SolveTask *tasks, const FrontD *fr, const i64 *Ls,
     const double *Lx, double *W)
 {
@@ -714,7 +725,7 @@ __global__ void __launch_bounds__(256) k_sd_lsolve (const SolveTask *tasks, cons
     for (int jb = 0 ; jb < nscol ; jb += 16)
     {
         const int nb = nscol - jb < 16 ? nscol - jb : 16 ;
-        sd_stage_diag (L, nsrow, jb, nb, Dl, tid) ;
+        sd_stage_diag<CX> (L, nsrow, jb, nb, Dl, tid) ;
         __syncthreads () ;
         if (tid < 16)
         {
@@ -734,7 +745,7 @@ __global__ void __launch_bounds__(256) k_sd_lsolve (const SolveTask *tasks, cons
         __syncthreads () ;
         for (int i0 = jb + 16 + 16 * wave ; i0 < nscol ; i0 += 64)
         {
-            const d4 p = sd_mul_nx (L + (i64) jb * nsrow, nsrow, i0, nscol, nb, x1 + jb * SD_NP, sd_zero (), lr, lk) ;
+            const d4 p = sd_mul_nx<CX> (L + colx<CX> (jb, nsrow), nsrow, i0, nscol, nb, x1 + jb * SD_NP, sd_zero (), lr, lk) ;
 #pragma unroll
             for (int r = 0 ; r < 4 ; r++)
             {
@@ -748,7 +759,7 @@ __global__ void __launch_bounds__(256) k_sd_lsolve (const SolveTask *tasks, cons
     if (T.below)
         for (int i0 = nscol + 16 * wave ; i0 < nsrow ; i0 += 64)
         {
-            const d4 p = sd_mul_nx (L, nsrow, i0, nsrow, nscol, x1, sd_zero (), lr, lk) ;
+            const d4 p = sd_mul_nx<CX> (L, nsrow, i0, nsrow, nscol, x1, sd_zero (), lr, lk) ;
 #pragma unroll
             for (int r = 0 ; r < 4 ; r++)
             {
@@ -760,6 +771,7 @@ __global__ void __launch_bounds__(256) k_sd_lsolve (const SolveTask *tasks, cons
 
 // backward: x1 -= L2' W [Ls2] (the rows split over the four waves, their partial tiles summed in a fixed order: no
 // atomics), then x1 = L1' \ x1 by 16-column blocks from the bottom
+template <bool CX>
 __global__ void __launch_bounds__(256) k_sd_ltsolve (const SolveTask *tasks, const FrontD *fr, const i64 *Ls,
     const double *Lx, double *W)
 {
@@ -780,7 +792,7 @@ __global__ void __launch_bounds__(256) k_sd_ltsolve (const SolveTask *tasks, con
         auto yg = [&] (int i, int c) { return W [rows [i] * SD_NP + c] ; } ;
         for (int j0 = 0 ; j0 < nscol ; j0 += 16)
         {
-            const d4 p = sd_mul_ty (L, nsrow, j0, nscol, nscol + 16 * wave, nsrow, 64, yg, sd_zero (), lr, lk) ;
+            const d4 p = sd_mul_ty<CX> (L, nsrow, j0, nscol, nscol + 16 * wave, nsrow, 64, yg, sd_zero (), lr, lk) ;
 #pragma unroll
             for (int r = 0 ; r < 4 ; r++) red [wave][(lk + 4 * r) * SD_NP + lr] = p [r] ;
             __syncthreads () ;
@@ -793,7 +805,7 @@ __global__ void __launch_bounds__(256) k_sd_ltsolve (const SolveTask *tasks, con
     for (int jb = ((nscol - 1) / 16) * 16 ; jb >= 0 ; jb -= 16)
     {
         const int nb = nscol - jb < 16 ? nscol - jb : 16 ;
-        sd_stage_diag (L, nsrow, jb, nb, Dl, tid) ;
+        sd_stage_diag<CX> (L, nsrow, jb, nb, Dl, tid) ;
         __syncthreads () ;
         if (tid < 16)
         {
@@ -814,7 +826,7 @@ __global__ void __launch_bounds__(256) k_sd_ltsolve (const SolveTask *tasks, con
         // the columns before the block: x1 [0, jb) -= L [jb .. jb+nb, 0 .. jb)' x1 [jb .. jb+nb)
         for (int j0 = 16 * wave ; j0 < jb ; j0 += 64)
         {
-            const d4 p = sd_mul_ty (L, nsrow, j0, jb, jb, jb + nb, 16, ys, sd_zero (), lr, lk) ;
+            const d4 p = sd_mul_ty<CX> (L, nsrow, j0, jb, jb, jb + nb, 16, ys, sd_zero (), lr, lk) ;
 #pragma unroll
             for (int r = 0 ; r < 4 ; r++) x1 [(j0 + lk + 4 * r) * SD_NP + lr] -= p [r] ;
         }
@@ -827,6 +839,7 @@ __global__ void __launch_bounds__(256) k_sd_ltsolve (const SolveTask *tasks, con
 // forward, step 1 (one workgroup per task): x_b = inv (L_bb) x_b by 64-column sub-blocks, in place in W.  Wave =
 // 16 rows of the sub-block: t = x_k - L [sub-block k, columns before it] x (solved), then x_k = W_k t with the
 // explicit inverse, both as tiles.
+template <bool CX>
 __global__ void __launch_bounds__(256) k_sd_fwd_diag (const SolveBlk *tasks, const FrontD *fr, const double *Lx,
     const double *Winv, double *W)
 {
@@ -837,18 +850,18 @@ __global__ void __launch_bounds__(256) k_sd_fwd_diag (const SolveBlk *tasks, con
     const int nsrow = f.nsrow, tid = threadIdx.x ;
     const int jb = T.jb, w = T.w, nsub = (w + 63) >> 6 ;
     const int lane = tid & 63, wave = tid >> 6, lr = lane & 15, lk = lane >> 4 ;
-    const double *Lbb = Lx + f.psx + jb + (i64) jb * nsrow ;
+    const double *Lbb = Lx + f.psx + jb + colx<CX> (jb, nsrow) ;
     double *Wk = W + (i64) (f.k1 + jb) * SD_NP ;
     for (int e = tid ; e < SOLVE_SB * SD_NP ; e += 256) xs [e] = (e < w * SD_NP) ? Wk [e] : 0.0 ;
     __syncthreads () ;
     for (int k = 0 ; k < nsub ; k++)
     {
         const int i0 = 64 * k + 16 * wave ;
-        const d4 p = sd_mul_nx (Lbb, nsrow, i0, w, 64 * k, xs, sd_zero (), lr, lk) ;
+        const d4 p = sd_mul_nx<CX> (Lbb, nsrow, i0, w, 64 * k, xs, sd_zero (), lr, lk) ;
 #pragma unroll
         for (int r = 0 ; r < 4 ; r++) ts [(16 * wave + lk + 4 * r) * SD_NP + lr] = xs [(i0 + lk + 4 * r) * SD_NP + lr] - p [r] ;
         __syncthreads () ;
-        const d4 q = sd_mul_nx (Winv + (i64) (T.inv + k) * 8192, 64, 16 * wave, 64, 64, ts, sd_zero (), lr, lk) ;
+        const d4 q = sd_mul_nx<false> (Winv + (i64) (T.inv + k) * 8192, 64, 16 * wave, 64, 64, ts, sd_zero (), lr, lk) ;
 #pragma unroll
         for (int r = 0 ; r < 4 ; r++) xs [(i0 + lk + 4 * r) * SD_NP + lr] = q [r] ;
         __syncthreads () ;
@@ -858,6 +871,7 @@ __global__ void __launch_bounds__(256) k_sd_fwd_diag (const SolveBlk *tasks, con
 
 // forward, step 2: W [rows below the block] -= L [rows, b] x_b ; workgroup = (256-row chunk) x (64-column
 // sub-block), wave = 64 of the rows as four tiles that share the x_b operand
+template <bool CX>
 __global__ void __launch_bounds__(256) k_sd_fwd_apply (const SolveBlk *tasks, int ntasks, const FrontD *fr,
     const i64 *Ls, const double *Lx, double *W)
 {
@@ -870,7 +884,7 @@ __global__ void __launch_bounds__(256) k_sd_fwd_apply (const SolveBlk *tasks, in
     const int wgl = (int) blockIdx.x - T.wg_start ;
     const int q = wgl % nsub, chunk = wgl / nsub ;
     const int c0 = 64 * q, cw = (w - c0 < 64) ? w - c0 : 64 ;
-    const double *L = Lx + f.psx + (i64) (jb + c0) * nsrow ;
+    const double *L = Lx + f.psx + colx<CX> (jb + c0, nsrow) ;
     const i64 *rows = Ls + f.psi ;
     const double *Wb = W + (i64) (k1 + jb + c0) * SD_NP ;
     for (int e = tid ; e < 64 * SD_NP ; e += 256) xs [e] = (e < cw * SD_NP) ? Wb [e] : 0.0 ;
@@ -879,13 +893,15 @@ __global__ void __launch_bounds__(256) k_sd_fwd_apply (const SolveBlk *tasks, in
     if (rb >= nsrow) return ;
     d4 acc [4] = {sd_zero (), sd_zero (), sd_zero (), sd_zero ()} ;
     bool rok [4] ;
+    int ri [4] ;
     const double *Li [4] ;
 #pragma unroll
     for (int t = 0 ; t < 4 ; t++)
     {
         const int i = rb + 16 * t + lr ;
         rok [t] = i < nsrow ;
-        Li [t] = L + (rok [t] ? i : rb) ;
+        ri [t] = rok [t] ? i : rb ;
+        Li [t] = L + ri [t] ;
     }
     for (int k0 = 0 ; k0 < cw ; k0 += 4)
     {
@@ -894,7 +910,7 @@ __global__ void __launch_bounds__(256) k_sd_fwd_apply (const SolveBlk *tasks, in
         const double b = ok ? xs [k * SD_NP + lr] : 0.0 ;
         double a [4] ;
 #pragma unroll
-        for (int t = 0 ; t < 4 ; t++) a [t] = (ok && rok [t]) ? Li [t][(i64) k * nsrow] : 0.0 ;
+        for (int t = 0 ; t < 4 ; t++) a [t] = (ok && rok [t]) ? (CX ? ldcx<CX> (L, ri [t], k, nsrow) : Li [t][(i64) k * nsrow]) : 0.0 ;
 #pragma unroll
         for (int t = 0 ; t < 4 ; t++) acc [t] = __builtin_amdgcn_mfma_f64_16x16x4f64 (a [t], b, acc [t], 0, 0, 0) ;
     }
@@ -912,6 +928,7 @@ __global__ void __launch_bounds__(256) k_sd_fwd_apply (const SolveBlk *tasks, in
 // backward, step 1: acc (task) += L [rows, b]' W [rows] ; workgroup = (256-row chunk) x (64-column sub-block);
 // the gathered rows are staged in LDS once, wave = 16 of the columns, one atomic add per column, right-hand side
 // and workgroup.  acc: [slot][256][16].
+template <bool CX>
 __global__ void __launch_bounds__(256) k_sd_bwd_apply (const SolveBlk *tasks, int ntasks, const FrontD *fr,
     const i64 *Ls, const double *Lx, const double *W, double *accbuf)
 {
@@ -938,7 +955,7 @@ __global__ void __launch_bounds__(256) k_sd_bwd_apply (const SolveBlk *tasks, in
     const int c0 = 64 * qsub + 16 * wave ;
     if (c0 >= w) return ;
     auto yl = [&] (int i, int c) { return ys [(i - r0) * SD_NP + c] ; } ;
-    const d4 p = sd_mul_ty (L, nsrow, jb + c0, jb + w, r0, r0 + nr, 16, yl, sd_zero (), lr, lk) ;
+    const d4 p = sd_mul_ty<CX> (L, nsrow, jb + c0, jb + w, r0, r0 + nr, 16, yl, sd_zero (), lr, lk) ;
 #pragma unroll
     for (int r = 0 ; r < 4 ; r++)
     {
@@ -949,6 +966,7 @@ __global__ void __launch_bounds__(256) k_sd_bwd_apply (const SolveBlk *tasks, in
 
 // backward, step 2 (one workgroup per task): x_b = inv (L_bb)' (x_b - acc) by sub-blocks from the bottom; the
 // accumulator is cleared for the next step
+template <bool CX>
 __global__ void __launch_bounds__(256) k_sd_bwd_diag (const SolveBlk *tasks, const FrontD *fr, const double *Lx,
     const double *Winv, double *W, double *accbuf)
 {
@@ -959,7 +977,7 @@ __global__ void __launch_bounds__(256) k_sd_bwd_diag (const SolveBlk *tasks, con
     const int nsrow = f.nsrow, tid = threadIdx.x ;
     const int jb = T.jb, w = T.w, nsub = (w + 63) >> 6 ;
     const int lane = tid & 63, wave = tid >> 6, lr = lane & 15, lk = lane >> 4 ;
-    const double *Lbb = Lx + f.psx + jb + (i64) jb * nsrow ;
+    const double *Lbb = Lx + f.psx + jb + colx<CX> (jb, nsrow) ;
     double *acc = accbuf + (i64) T.slot * SOLVE_SB * SD_NP ;
     double *Wk = W + (i64) (f.k1 + jb) * SD_NP ;
     for (int e = tid ; e < SOLVE_SB * SD_NP ; e += 256)
@@ -973,11 +991,11 @@ __global__ void __launch_bounds__(256) k_sd_bwd_diag (const SolveBlk *tasks, con
     {
         const int c0 = 64 * k + 16 * wave ;
         // t = x_k - sum over the solved rows below sub-block k (inside the block) of L (row, column)' x (row)
-        const d4 p = sd_mul_ty (Lbb, nsrow, c0, w, 64 * (k + 1), w, 16, yl, sd_zero (), lr, lk) ;
+        const d4 p = sd_mul_ty<CX> (Lbb, nsrow, c0, w, 64 * (k + 1), w, 16, yl, sd_zero (), lr, lk) ;
 #pragma unroll
         for (int r = 0 ; r < 4 ; r++) ts [(16 * wave + lk + 4 * r) * SD_NP + lr] = xs [(c0 + lk + 4 * r) * SD_NP + lr] - p [r] ;
         __syncthreads () ;
-        const d4 q = sd_mul_nx (Winv + (i64) (T.inv + k) * 8192 + 4096, 64, 16 * wave, 64, 64, ts, sd_zero (), lr, lk) ;
+        const d4 q = sd_mul_nx<false> (Winv + (i64) (T.inv + k) * 8192 + 4096, 64, 16 * wave, 64, 64, ts, sd_zero (), lr, lk) ;
 #pragma unroll
         for (int r = 0 ; r < 4 ; r++) xs [(c0 + lk + 4 * r) * SD_NP + lr] = q [r] ;
         __syncthreads () ;

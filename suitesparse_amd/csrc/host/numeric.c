@@ -1129,6 +1129,96 @@ int cholmod_l_hip_refine_device (cholmod_factor *L, const double *B_dev, size_t 
         steps, Rnorm_dev, stream), Common, "HIP device refinement failed") ;
 }
 
+/* ---- the same three for a complex factor (cholmod.h) ----------------------------------------------------------------
+ * The solves with L and L^H are the real solves with the twin on the interleaved right-hand side, the same bytes
+ * (complex.c): the twin's plan gets 2 ld doubles per column and the same nrhs.  The twin's own Perm is the identity (the
+ * matrix it was factorized from is already permuted), so the plan is handed the complex factor's permutation expanded
+ * to the twin's rows, once per twin (T->hip_perm_set; a new plan clears it). */
+
+/* what the three check alike, before any device call; TRUE: *plan is the twin's, ready (NULL: nothing to do) */
+static int complex_device_ready (cholmod_factor *L, size_t ld1, size_t ld2, size_t ld3, size_t nrhs, cholmod_hip_plan **plan,
+    cholmod_common *Common)
+{
+    *plan = NULL ;
+    if (ld1 < L->n || ld2 < L->n || ld3 < L->n) { ERROR (CHOLMOD_INVALID, "leading dimension smaller than n") ; return FALSE ; }
+    if (L->xtype == CHOLMOD_ZOMPLEX) { ERROR (CHOLMOD_NOT_INSTALLED, "zomplex factors are not supported") ; return FALSE ; }
+    if (L->xtype != CHOLMOD_COMPLEX || !L->is_super)
+    { ERROR (CHOLMOD_INVALID, "L must be a complex numeric supernodal factor (a real L: cholmod_l_hip_solve_device)") ; return FALSE ; }
+    if (ssamd_resolve_use_gpu (Common) != 1) { ERROR (CHOLMOD_INVALID, "device arrays need Common->useGPU") ; return FALSE ; }
+    if (Common->hip_world > 1) { ERROR (CHOLMOD_INVALID, "complex device arrays are served on one rank only") ; return FALSE ; }
+    cholmod_factor *T = (cholmod_factor *) L->cx_twin ;
+    if (!T || !T->hip_plan || !T->hip_on_device)
+    { ERROR (CHOLMOD_INVALID, "L was not factorized on the device") ; return FALSE ; }
+    Common->status = CHOLMOD_OK ;
+    if (nrhs == 0 || L->n == 0) return TRUE ;
+    if (!T->hip_perm_set)
+    {
+        const Int n = (Int) L->n, *Perm = L->Perm ;
+        int64_t *P2 = cholmod_l_malloc (2 * (size_t) n, sizeof (int64_t), Common) ;
+        if (!P2) return FALSE ;
+        for (Int k = 0 ; k < n ; k++) { P2 [2*k] = 2 * (int64_t) Perm [k] ; P2 [2*k+1] = 2 * (int64_t) Perm [k] + 1 ; }
+        int rc = cholmod_hip_set_perm ((cholmod_hip_plan *) T->hip_plan, P2) ;
+        cholmod_l_free (2 * (size_t) n, sizeof (int64_t), P2, Common) ;
+        if (rc != CHOLMOD_HIP_OK) return map_hip_status (rc, Common, "the permutation could not be stored on the device") ;
+        T->hip_perm_set = TRUE ;
+    }
+    *plan = (cholmod_hip_plan *) T->hip_plan ;
+    return TRUE ;
+}
+
+int cholmod_l_hip_solve_device_complex (int sys, cholmod_factor *L, const void *B_dev, size_t ldb, void *X_dev, size_t ldx,
+    size_t nrhs, void *stream, cholmod_common *Common)
+{
+    RETURN_IF_NULL_COMMON (FALSE) ;
+    RETURN_IF_NULL (L, FALSE) ;
+    RETURN_IF_NULL (B_dev, FALSE) ;
+    RETURN_IF_NULL (X_dev, FALSE) ;
+    if (sys < CHOLMOD_A || sys > CHOLMOD_Pt) { ERROR (CHOLMOD_INVALID, "invalid system") ; return FALSE ; }
+    cholmod_hip_plan *plan ;
+    if (!complex_device_ready (L, ldb, ldx, ldx, nrhs, &plan, Common)) return FALSE ;
+    if (!plan) return TRUE ;
+    /* as in cholmod_l_hip_solve_device: L' of the twin is L^H of the complex factor */
+    const int perm_in = (sys == CHOLMOD_A || sys == CHOLMOD_P), perm_out = (sys == CHOLMOD_A || sys == CHOLMOD_Pt) ;
+    const int which = (sys == CHOLMOD_A || sys == CHOLMOD_LDLt) ? 0
+                    : (sys == CHOLMOD_L || sys == CHOLMOD_LD) ? 1
+                    : (sys == CHOLMOD_Lt || sys == CHOLMOD_DLt) ? 2 : 3 ;
+    int rc = cholmod_hip_solve_device (plan, which, perm_in, perm_out, (const double *) B_dev, (int64_t) (2 * ldb),
+        (double *) X_dev, (int64_t) (2 * ldx), (int64_t) nrhs, stream) ;
+    return (rc == CHOLMOD_HIP_OK) ? TRUE : map_hip_status (rc, Common, "HIP device solve failed") ;
+}
+
+int cholmod_l_hip_residual_device_complex (cholmod_factor *L, const void *X_dev, size_t ldx, const void *B_dev, size_t ldb,
+    void *R_dev, size_t ldr, size_t nrhs, double *Rnorm_dev, void *stream, cholmod_common *Common)
+{
+    RETURN_IF_NULL_COMMON (FALSE) ;
+    RETURN_IF_NULL (L, FALSE) ;
+    RETURN_IF_NULL (X_dev, FALSE) ;
+    RETURN_IF_NULL (B_dev, FALSE) ;
+    RETURN_IF_NULL (R_dev, FALSE) ;
+    if (R_dev == X_dev) { ERROR (CHOLMOD_INVALID, "R must not be X") ; return FALSE ; }
+    cholmod_hip_plan *plan ;
+    if (!complex_device_ready (L, ldx, ldb, ldr, nrhs, &plan, Common)) return FALSE ;
+    if (!plan) return TRUE ;
+    return residual_status (cholmod_hip_residual_device (plan, 1, (const double *) X_dev, (int64_t) (2 * ldx),
+        (const double *) B_dev, (int64_t) (2 * ldb), (double *) R_dev, (int64_t) (2 * ldr), (int64_t) nrhs, Rnorm_dev, stream),
+        Common, "HIP device residual failed") ;
+}
+
+int cholmod_l_hip_refine_device_complex (cholmod_factor *L, const void *B_dev, size_t ldb, void *X_dev, size_t ldx,
+    size_t nrhs, int steps, double *Rnorm_dev, void *stream, cholmod_common *Common)
+{
+    RETURN_IF_NULL_COMMON (FALSE) ;
+    RETURN_IF_NULL (L, FALSE) ;
+    RETURN_IF_NULL (B_dev, FALSE) ;
+    RETURN_IF_NULL (X_dev, FALSE) ;
+    if (steps < 0) { ERROR (CHOLMOD_INVALID, "steps must not be negative") ; return FALSE ; }
+    cholmod_hip_plan *plan ;
+    if (!complex_device_ready (L, ldb, ldx, ldx, nrhs, &plan, Common)) return FALSE ;
+    if (!plan) return TRUE ;
+    return residual_status (cholmod_hip_refine_device (plan, 1, (const double *) B_dev, (int64_t) (2 * ldb), (double *) X_dev,
+        (int64_t) (2 * ldx), (int64_t) nrhs, steps, Rnorm_dev, stream), Common, "HIP device refinement failed") ;
+}
+
 /* the triangular solves run where the factor is: on the host when the values are
  * in L->x and the engine is not to be used (Common->useGPU == 0, no device, or a
  * factor the CPU path computed) */
