@@ -502,6 +502,32 @@ int cholmod_l_hip_aat_values_grad_device (cholmod_sparse *A, cholmod_factor *L, 
     cholmod_common *Common) ;
 int cholmod_l_hip_aat_logdet_grad_device (cholmod_sparse *A, cholmod_factor *L, const double *Avalues_dev, double *G_dev,
     void *stream, cholmod_common *Common) ;
+/* The gradient THROUGH THE FACTOR (csrc/host/factor_grad.c; the engine's cholmod_hip_factor_grad_*: reverse-mode Cholesky,
+ * the sweep of the selected inverse with another recurrence).  For a scalar f of the entries of L -- a reparameterised
+ * sample P' inv (L') z, a whitened vector inv (L) P b, any function of L --, with L L' = P (A + beta I) P':
+ * cholmod_l_hip_factor_grad_device takes Lbar_dev = df/dL (L->xsize doubles on the device in the layout of L->x, read only;
+ * the dead upper triangles of the diagonal blocks are ignored); cholmod_l_hip_factor_outer_grad_device forms
+ * Lbar (i, j) = alpha sum_{r < nrhs} P (i, r) Q (j, r) on the pattern of L itself, P_dev and Q_dev n-by-nrhs, column-major, on
+ * the device, in the FACTOR's ordering (what cholmod_l_hip_solve_device returns for CHOLMOD_L and CHOLMOD_Lt), read only,
+ * possibly the same array.  For x = inv (L') z and an incoming gx, with u = inv (L) gx:  P = x, Q = u, alpha = -1, and the
+ * gradient with respect to z is u; for y = inv (L) b and gy, with v = inv (L') gy:  P = v, Q = y, alpha = -1, and the one
+ * with respect to b is v.
+ * G_dev (NULL, or nnz (A) doubles on the device, A's entry order) receives df/d (the value of A at that entry): for an entry
+ * the factorization reads, df/dS at the stored entry of the lower-stored S it is read into; exact +0.0 at every other
+ * entry.  trace_dev (NULL, or one double on the device) receives df/dbeta, the trace of df/dS.  A gives the PATTERN only and
+ * is hashed against L->hip_apat_* exactly as cholmod_l_hip_selinv_device does; A == NULL is legal when G_dev is.
+ * cholmod_l_hip_factor_grad_to_host: Gx receives the whole of df/dS on the pattern of L, L->xsize doubles indexed like L->x,
+ * of the last of the two calls above; it waits for it.  A factorization since then makes it stale: CHOLMOD_INVALID.
+ * The calls take their place on `stream` as cholmod_l_hip_selinv_device does; the same inputs give the same bits.
+ * FALSE with CHOLMOD_INVALID for NULL pointers, a symbolic L, L->minor < n, the GPU switched off (no host fallback), several
+ * ranks, an L not factorized on the device, a leading dimension smaller than n; with G_dev also for an unsymmetric
+ * (stype == 0) or unpacked A, mismatched dimensions, an L without the pattern record; with CHOLMOD_NOT_INSTALLED for a complex
+ * or zomplex A or L -- all before a device is touched. */
+int cholmod_l_hip_factor_grad_device (cholmod_sparse *A, cholmod_factor *L, const double *Lbar_dev, double *G_dev,
+    double *trace_dev, void *stream, cholmod_common *Common) ;
+int cholmod_l_hip_factor_outer_grad_device (cholmod_sparse *A, cholmod_factor *L, double alpha, const double *P_dev, size_t ldp,
+    const double *Q_dev, size_t ldq, size_t nrhs, double *G_dev, double *trace_dev, void *stream, cholmod_common *Common) ;
+int cholmod_l_hip_factor_grad_to_host (cholmod_factor *L, double *Gx, cholmod_common *Common) ;
 /* cholmod_l_factorize for new VALUES of A that already live in device memory (a matrix assembled on the GPU: the step of a
  * Newton, time-stepping or interior-point loop), without a trip through the host.  A supplies the PATTERN only (p, i,
  * stype, packed; A->x is never read and may be NULL); Ax_dev is a device pointer to nnz (A) doubles in A's own entry

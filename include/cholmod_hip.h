@@ -421,12 +421,57 @@ int cholmod_hip_selinv_gather_device (cholmod_hip_plan *plan, double *dZvalues, 
     void *stream) ;
 /* Zx (xsize doubles) to the host; waits for the engine stream.  CHOLMOD_HIP_INVALID without a current Zx. */
 int cholmod_hip_selinv_download (cholmod_hip_plan *plan, double *Zx_host) ;
-/* frees Zx and the scratch (the launch program stays); the next cholmod_hip_selinv_device allocates them again */
+/* frees Zx and the scratch -- unless a Gx of the factor gradient shares it -- (the launch program stays); the next cholmod_hip_selinv_device allocates them again */
 int cholmod_hip_selinv_release (cholmod_hip_plan *plan) ;
 /* out8: [0] device seconds of the last cholmod_hip_selinv_device (two events, read here: may wait for it)  [1] its kernel
  * launches  [2] flops of the hot product, sum of 2 |R|^2 nb over the blocks  [3] all flops  [4] bytes of Zx  [5] bytes of
  * scratch  [6] 1 if Zx is current  [7] reserved, zero */
 int cholmod_hip_selinv_info (cholmod_hip_plan *plan, double *out8) ;
+
+/* (This entry point and the five after it: csrc/hip/factor_grad.hip.)
+ * The gradient through the factor (reverse-mode Cholesky): given Lbar = df/dL on the pattern of L, Gx = df/dS on the
+ * pattern of L, where S = L L' = P (A + beta I) P' is LOWER-STORED -- an off-diagonal entry stands for two entries of the
+ * symmetric matrix, Gx at (i, j), i >= j, is the derivative with respect to that stored entry.  Gx is a further array of
+ * xsize doubles in HBM in exactly the layout of Lx, the dead strictly-upper triangle of every diagonal block exact +0.0.
+ * dLbar: xsize doubles on the device in the layout of Lx, read only; what stands in its dead triangles is ignored.
+ * The sweep is that of the selected inverse -- its launch program, its scratch, both shared -- with another recurrence:
+ * per block, with W = Gx [R, R] and M = W + W', Gx [R, b] = (Lbar [R, b] - M L [R, b]) inv (L_bb) on v_mfma_f64_16x16x4,
+ * Gx [b, b] from tril (Lbar [b, b]) - tril (Gx [R, b]' L [R, b]) through a triangular product and two triangular solves.
+ * The selected inverse is the special case Lbar = diag (2 / L_jj): then Gx = Z on the diagonal and 2 Z off it.  Every
+ * entry has one owner and a fixed summation order: two calls on the same inputs give the same bits.
+ * Ordered on `stream` exactly as cholmod_hip_selinv_device is; the first call allocates Gx (and the program and the
+ * scratch, if the selected inverse has not), after that nothing is allocated and the host does not wait.  Not during
+ * capture.  Gx stays resident until cholmod_hip_factor_grad_release or cholmod_hip_plan_destroy; any factorization,
+ * cholmod_hip_upload_factor or cholmod_hip_upload_matrix marks it stale.  Zx and Gx are separate arrays with separate
+ * staleness.
+ * All six return CHOLMOD_HIP_INVALID, before any device call, for a NULL plan or pointer, a host-only plan, several ranks,
+ * no numeric factor on the device, a last factorization that was not positive definite, and the plans of complex factors;
+ * CHOLMOD_HIP_OUT_OF_MEMORY when Gx and the scratch do not fit: what the call allocated is freed, the factor is untouched. */
+int cholmod_hip_factor_grad_device (cholmod_hip_plan *plan, const double *dLbar, void *stream) ;
+/* The same sweep with Lbar (i, j) = alpha sum_{r < nrhs} P (i, r) Q (j, r) on the pattern of L, r in index order, formed by a
+ * kernel straight into Gx: no xsize array of the caller exists.  dP, dQ: n-by-nrhs, column-major, on the device, in the
+ * FACTOR's ordering, read only (dP == dQ is legal); nrhs == 0 gives a zero Lbar.  With x = inv (L') z, an incoming gx and
+ * u = inv (L) gx:  P = x, Q = u, alpha = -1 is the gradient through the solve with L', and gz = u; with y = inv (L) b, an
+ * incoming gy and v = inv (L') gy:  P = v, Q = y, alpha = -1 the one through the solve with L, and gb = v.
+ * CHOLMOD_HIP_INVALID also for ldp < n, ldq < n, nrhs < 0. */
+int cholmod_hip_factor_outer_grad_device (cholmod_hip_plan *plan, double alpha, const double *dP, int64_t ldp, const double *dQ,
+    int64_t ldq, int64_t nrhs, void *stream) ;
+/* What a caller takes from a current Gx, on the device and ordered on `stream` as above; either pointer may be NULL.
+ * dG [k], k < nvalues in the order of the value map, receives Gx at the entry the resident S reads value k into -- the
+ * gradient with respect to that value -- and exact +0.0 where the factorization does not read the value (the rule of
+ * cholmod_hip_values_grad_device, not the NaN of cholmod_hip_selinv_gather_device).  dTrace [0] receives sum_j Gx (j, j), the
+ * gradient with respect to beta, summed in a fixed tree without floating-point atomics.  CHOLMOD_HIP_INVALID also: no
+ * current Gx; dG without a value map of the current resident packed S, with another nvalues than the map's, or with a
+ * product map set. */
+int cholmod_hip_factor_grad_gather_device (cholmod_hip_plan *plan, double *dG, int64_t nvalues, double *dTrace, void *stream) ;
+/* Gx (xsize doubles) to the host; waits for the engine stream.  CHOLMOD_HIP_INVALID without a current Gx. */
+int cholmod_hip_factor_grad_download (cholmod_hip_plan *plan, double *Gx_host) ;
+/* frees Gx, and the scratch unless a Zx shares it (the launch program stays); the next sweep allocates them again */
+int cholmod_hip_factor_grad_release (cholmod_hip_plan *plan) ;
+/* out8: the figures of cholmod_hip_selinv_info for the last sweep of the two entry points above: [0] its device seconds
+ * [1] its launches (the program's and the one that forms Lbar)  [2] flops of the hot product  [3] all flops of the
+ * program  [4] bytes of Gx  [5] bytes of scratch  [6] 1 if Gx is current  [7] reserved, zero */
+int cholmod_hip_factor_grad_info (cholmod_hip_plan *plan, double *out8) ;
 
 /* (This entry point and the next: csrc/hip/grad.hip.)
  * The gradient with respect to the values of A, sampled on the pattern of the resident S.  dU, dV: n-by-nrhs, column-major,

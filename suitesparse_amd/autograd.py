@@ -4,6 +4,8 @@ the device and on torch's current stream.
     chol = DeviceCholesky(session, A, Lf, beta=0.0)
     X = chol.solve(values, B)           # M^-1 B; differentiable in values, B and (a tensor) beta
     ld = chol.logdet(values)            # log det M; differentiable in values and (a tensor) beta
+    X = chol.solve_Lt(values, Z)        # P' L^-T Z, the reparameterised sample from N (0, M^-1); symmetric A only
+    Y = chol.solve_L(values, B)         # L^-1 P B, whitening; both differentiable in values, the right-hand side and beta
 
 `A` gives the pattern, `values` (a 1-D torch.float64 device tensor of length nnz (A), A's entry order) the numbers, `Lf` is a
 factor that was factorized once from a host matrix of A's pattern -- the precondition of Session.factorize_device.  For a
@@ -18,6 +20,13 @@ the one with respect to the values of an unsymmetric A; its trace, -(Lambda . X)
 The gradient of log det M with respect to M is Z = M^-1 from Session.selinv_device: Z_ii on the diagonal and 2 Z_ij off it
 for the value of a symmetric A at (i, j), Session.aat_logdet_grad_device for an unsymmetric A, Z's trace for beta.
 
+solve_Lt and solve_L are functions of the factor L L' = P M P' itself, and their gradient with respect to M is neither low
+rank nor the inverse: it is reverse-mode Cholesky (Session.factor_outer_grad_device, the sweep of the selected inverse with
+another recurrence).  With Xt = L^-T Z and an incoming gradient gXt (the factor's ordering), U = L^-1 gXt is the gradient
+with respect to Z and Lbar = -tril (Xt U') the one with respect to L; with Y = L^-1 P B and gY, V = L^-T gY gives P' V for B
+and Lbar = -tril (V Y').  The sweep turns Lbar into the gradient with respect to the values of A -- zero where the
+factorization does not read A -- and its trace, the gradient with respect to beta.
+
 beta is a Python float, or a 0-dim torch.float64 tensor on either device; a tensor that requires grad receives its
 gradient (two torch reductions on the current stream).  The factorization reads float (beta) -- it waits for the host
 anyway --, once per version of the tensor.
@@ -25,7 +34,7 @@ anyway --, once per version of the tensor.
 The wrapper OWNS Lf: a factorization of Lf behind its back is detected (the engine counts factorizations,
 cholmod_hip_progress out [0]) and answered by factorizing again from the values a backward pass saved, but values handed to
 Session.factorize_device directly are not seen by `solve` / `logdet` calls that follow with the tensor factorized last.
-Both functions are differentiable once; real factors, one rank."""
+All functions are differentiable once; real factors, one rank."""
 import ctypes as C
 
 import numpy as np
@@ -124,6 +133,61 @@ class DeviceCholesky:
     def logdet(self, values):
         """log det M as a 0-dim device tensor"""
         return _LogDet.apply(self, values, self._beta_input())
+
+    def solve_Lt(self, values, Z):
+        """X = P' L^-T Z with L L' = P M P'; Z of shape (nrhs, n) or (n,), rows are right-hand sides.  For Z ~ N (0, I) the
+        rows of X are samples from N (0, M^-1).  A symmetric A (stype != 0) only."""
+        if self.aat:
+            raise NotImplementedError("DeviceCholesky.solve_Lt: A*A' input (stype == 0) is not supported")
+        return _SolveFactor.apply(self, values, Z, self._beta_input(), True)
+
+    def solve_L(self, values, B):
+        """Y = L^-1 P B with L L' = P M P': whitening, |Y|^2 = B' M^-1 B; B as for `solve_Lt`.  A symmetric A only."""
+        if self.aat:
+            raise NotImplementedError("DeviceCholesky.solve_L: A*A' input (stype == 0) is not supported")
+        return _SolveFactor.apply(self, values, B, self._beta_input(), False)
+
+
+class _SolveFactor(torch.autograd.Function):
+    """transposed: P' L^-T Z, else L^-1 P B"""
+
+    @staticmethod
+    def forward(ctx, chol, values, B, beta, transposed):
+        ctx.chol, ctx.fact, ctx.transposed = chol, chol._ensure(values), transposed
+        ctx.beta_device = None if beta is None else beta.device
+        S, Lf = chol.S, chol.Lf
+        B = B.detach().contiguous()
+        if transposed:
+            inner = S.solve_device(Lf, B, ch.SYS_Lt)            # Xt, the factor's ordering
+            out = S.solve_device(Lf, inner, ch.SYS_Pt)
+        else:
+            out = inner = S.solve_device(Lf, S.solve_device(Lf, B, ch.SYS_P), ch.SYS_L)
+        ctx.save_for_backward(values, inner)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        chol = ctx.chol
+        values, inner = ctx.saved_tensors
+        need_v, need_b, need_beta = ctx.needs_input_grad[1:4]
+        if not (need_v or need_b or need_beta):
+            return None, None, None, None, None
+        chol._restore(values, ctx.fact)
+        S, Lf = chol.S, chol.Lf
+        g = g.contiguous()
+        if ctx.transposed:
+            gb = other = S.solve_device(Lf, S.solve_device(Lf, g, ch.SYS_P), ch.SYS_L)      # U = L^-1 P gX
+            P, Q = inner, other                                                             # Lbar = -tril (Xt U')
+        else:
+            other = S.solve_device(Lf, g, ch.SYS_Lt)                                        # V = L^-T gY
+            gb = S.solve_device(Lf, other, ch.SYS_Pt)
+            P, Q = other, inner                                                             # Lbar = -tril (V Y')
+        gv = gbeta = None
+        if need_v or need_beta:
+            gv, tr = S.factor_outer_grad_device(chol.A, Lf, P, Q, alpha=-1.0)
+            gbeta = tr.to(ctx.beta_device) if need_beta else None
+        return None, (gv if need_v else None), (gb if need_b else None), gbeta, None
 
 
 class _Solve(torch.autograd.Function):

@@ -153,6 +153,7 @@ API_SYMBOLS = [
     "cholmod_l_hip_selinv_device", "cholmod_l_hip_selinv_to_host",
     "cholmod_l_hip_values_grad_device", "cholmod_l_hip_logdet_device",
     "cholmod_l_hip_aat_values_grad_device", "cholmod_l_hip_aat_logdet_grad_device",
+    "cholmod_l_hip_factor_grad_device", "cholmod_l_hip_factor_outer_grad_device", "cholmod_l_hip_factor_grad_to_host",
 ]
 HIP_SYMBOLS = [
     "cholmod_hip_probe", "cholmod_hip_memorysize", "cholmod_hip_set_device", "cholmod_hip_device_count",
@@ -168,6 +169,8 @@ HIP_SYMBOLS = [
     "cholmod_hip_get_maps", "cholmod_hip_get_stats", "cholmod_hip_set_profiling",
     "cholmod_hip_selinv_device", "cholmod_hip_selinv_gather_device", "cholmod_hip_selinv_download",
     "cholmod_hip_selinv_release", "cholmod_hip_selinv_info",
+    "cholmod_hip_factor_grad_device", "cholmod_hip_factor_outer_grad_device", "cholmod_hip_factor_grad_gather_device",
+    "cholmod_hip_factor_grad_download", "cholmod_hip_factor_grad_release", "cholmod_hip_factor_grad_info",
     "cholmod_hip_values_grad_device", "cholmod_hip_logdet_device",
     "cholmod_hip_product_values_grad_device", "cholmod_hip_product_logdet_grad_device",
     "cholmod_hip_dense_partial_factor", "cholmod_hip_factor_checks", "cholmod_hip_factor_checks_local", "cholmod_hip_get_launch_profile", "cholmod_hip_debug_thin_cycles", "cholmod_hip_debug_launch_regions",
@@ -319,6 +322,15 @@ def lib(hooks=None):
     sig("cholmod_hip_selinv_info", C.c_int, [vp, vp])
     sig("cholmod_l_hip_selinv_device", C.c_int, [sp, fc, vp, vp, vp, cm])
     sig("cholmod_l_hip_selinv_to_host", C.c_int, [fc, vp, cm])
+    sig("cholmod_hip_factor_grad_device", C.c_int, [vp, vp, vp])
+    sig("cholmod_hip_factor_outer_grad_device", C.c_int, [vp, dbl, vp, i64, vp, i64, i64, vp])
+    sig("cholmod_hip_factor_grad_gather_device", C.c_int, [vp, vp, i64, vp, vp])
+    sig("cholmod_hip_factor_grad_download", C.c_int, [vp, vp])
+    sig("cholmod_hip_factor_grad_release", C.c_int, [vp])
+    sig("cholmod_hip_factor_grad_info", C.c_int, [vp, vp])
+    sig("cholmod_l_hip_factor_grad_device", C.c_int, [sp, fc, vp, vp, vp, vp, cm])
+    sig("cholmod_l_hip_factor_outer_grad_device", C.c_int, [sp, fc, dbl, vp, sz, vp, sz, sz, vp, vp, vp, cm])
+    sig("cholmod_l_hip_factor_grad_to_host", C.c_int, [fc, vp, cm])
     sig("cholmod_hip_values_grad_device", C.c_int, [vp, C.c_int, dbl, vp, i64, vp, i64, i64, vp, i64, vp])
     sig("cholmod_hip_logdet_device", C.c_int, [vp, vp, vp])
     sig("cholmod_l_hip_values_grad_device", C.c_int, [sp, fc, dbl, vp, sz, vp, sz, sz, vp, vp, cm])
@@ -746,6 +758,62 @@ class Session:
         out = np.zeros(max(int(Lf.contents.xsize), 1))
         if not self.L.cholmod_l_hip_selinv_to_host(Lf, out.ctypes.data, C.byref(self.cm)):
             raise RuntimeError(f"cholmod_l_hip_selinv_to_host failed, status {self.cm.status}")
+        return out[:int(Lf.contents.xsize)]
+
+    def _factor_grad_outputs(self, A, dev):
+        """(G, trace) for the two factor-gradient calls: new torch.float64 tensors on `dev`, nnz (A) long and 0-dim"""
+        import torch
+        a = A.contents
+        nz = int(_view(a.p, a.ncol + 1, C.c_int64, np.int64)[-1]) if a.p else 0
+        return torch.zeros(nz, dtype=torch.float64, device=dev), torch.zeros((), dtype=torch.float64, device=dev)
+
+    def factor_grad_device(self, A, Lf, Lbar):
+        """cholmod_l_hip_factor_grad_device: reverse-mode Cholesky on the device.  Lbar: a 1-D contiguous torch.float64
+        device tensor of length L->xsize, df/dL in the layout of L->x (FactorView.x; the dead upper triangles of the
+        diagonal blocks are ignored).  Returns (G, trace): G a 1-D tensor of length nnz (A) in A's entry order, df/d (the
+        value of A at that entry), exact +0.0 where the factorization does not read A; trace a 0-dim tensor, df/dbeta.  A
+        gives the pattern only.  Enqueued on torch's current stream; the same inputs give the same bits."""
+        import torch
+        xsize = int(Lf.contents.xsize)
+        if not (isinstance(Lbar, torch.Tensor) and Lbar.is_cuda and Lbar.dtype == torch.float64):
+            raise TypeError("factor_grad_device: Lbar must be a torch.float64 tensor on the device")
+        if Lbar.dim() != 1 or Lbar.shape[0] != xsize or not Lbar.is_contiguous():
+            raise ValueError(f"factor_grad_device: Lbar must be 1-D, contiguous and of length L->xsize = {xsize}")
+        G, tr = self._factor_grad_outputs(A, Lbar.device)
+        stream = torch.cuda.current_stream(Lbar.device).cuda_stream
+        ok = self.L.cholmod_l_hip_factor_grad_device(A, Lf, Lbar.data_ptr() or 1, G.data_ptr() or 2, tr.data_ptr(), stream,
+                                                     C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_factor_grad_device failed, status {self.cm.status}")
+        return G, tr
+
+    def factor_outer_grad_device(self, A, Lf, P, Q, alpha=-1.0):
+        """cholmod_l_hip_factor_outer_grad_device: the same with Lbar = alpha sum_r P [:, r] Q [:, r]' sampled on the pattern
+        of L, formed on the device.  P, Q: device tensors as for `solve_device` (rows are right-hand sides), of one
+        shape, in the FACTOR's ordering -- what `solve_device` returns for sys=SYS_L and SYS_Lt --; they may be the same
+        tensor.  For Xt = solve_device (Lf, Z, SYS_Lt) and an incoming gradient gXt, with U = solve_device (Lf, gXt, SYS_L):
+        P = Xt, Q = U, alpha = -1 (and the gradient with respect to Z is U); for Y = solve_device (Lf, B, SYS_L) and gY, with
+        V = solve_device (Lf, gY, SYS_Lt):  P = V, Q = Y, alpha = -1 (and the gradient with respect to B is V).  Returns
+        (G, trace) as `factor_grad_device`."""
+        import torch
+        n = int(Lf.contents.n)
+        ldp, nrhs = self._device_layout("factor_outer_grad_device: P", n, P)
+        ldq, _ = self._device_layout("factor_outer_grad_device: Q", n, Q, like=P)
+        G, tr = self._factor_grad_outputs(A, P.device)
+        stream = torch.cuda.current_stream(P.device).cuda_stream
+        ok = self.L.cholmod_l_hip_factor_outer_grad_device(A, Lf, float(alpha), P.data_ptr() or 1, ldp, Q.data_ptr() or 1, ldq,
+                                                           nrhs, G.data_ptr() or 2, tr.data_ptr(), stream, C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_factor_outer_grad_device failed, status {self.cm.status}")
+        return G, tr
+
+    def factor_grad_host(self, Lf):
+        """cholmod_l_hip_factor_grad_to_host: Gx = df/dS on the pattern of L of the last factor_grad_device /
+        factor_outer_grad_device, in the layout of L->x (FactorView.x), xsize doubles, in the factor's ordering; waits for
+        it.  A factorization since then makes it stale: RuntimeError."""
+        out = np.zeros(max(int(Lf.contents.xsize), 1))
+        if not self.L.cholmod_l_hip_factor_grad_to_host(Lf, out.ctypes.data, C.byref(self.cm)):
+            raise RuntimeError(f"cholmod_l_hip_factor_grad_to_host failed, status {self.cm.status}")
         return out[:int(Lf.contents.xsize)]
 
     def solve_subset(self, Lf, b, bset, sys=SYS_A, handles=None):

@@ -422,7 +422,7 @@ static int factorize_prologue (cholmod_hip_plan *P)
 {
     hipStream_t st = P->stream ;
     P->winv_valid = false ;                 // the diagonal-block inverses follow the factor
-    P->si_valid = false ; P->factor_state = 0 ;     // ... and so does the selected inverse
+    P->si_valid = P->fg_valid = false ; P->factor_state = 0 ;     // ... and so do the selected inverse and the factor gradient
     HIPCHK (hipEventRecord (P->ev0, st)) ;
     // Lx := 0 (several ranks: the rank's own fronts -- its d_Lx holds nothing else); the complete
     // factor a gather may have left in d_Lx_full is stale from here on
@@ -948,7 +948,7 @@ int cholmod_hip_upload_matrix (cholmod_hip_plan *P, const int64_t *Sp, const int
     P->amap_valid = false ;         // a new pattern may have come with the new values
     P->rs_index_valid = false ;     // ... and the transposed index of the residual goes with the old one
     P->gr_index_valid = false ;     // ... and the column-of-entry array of the gradient
-    P->si_valid = false ;           // ... and the selected inverse is that of the old matrix
+    P->si_valid = P->fg_valid = false ;         // ... and the selected inverse and the factor gradient are those of the old matrix
     P->s_cur_nz = nz ;
     P->vsrc_nz = 0 ;                // ... and the value map of the previous one is void
     drop_product_map (P) ;          // ... with its product map
@@ -1254,7 +1254,7 @@ int cholmod_hip_upload_factor (cholmod_hip_plan *P, const double *Lx_host)
     }
     HIPCHK (hipMemcpy (Lw, Lx_host, P->xsize * sizeof (double), hipMemcpyHostToDevice)) ;
     P->winv_valid = false ;
-    P->si_valid = false ; P->factor_state = 1 ;
+    P->si_valid = P->fg_valid = false ; P->factor_state = 1 ;
     P->full_valid = P->world > 1 ;
     return CHOLMOD_HIP_OK ;
 }

@@ -403,8 +403,10 @@ struct cholmod_hip_plan {
     hipEvent_t rs_ev_out = nullptr ;
     // selected inverse (selinv.hip): its program, buffers and events live behind `si`.  factor_state follows the numeric
     // factor in d_Lx (0: none, 1: positive definite, 2: the last factorization was not); si_valid: Zx belongs to that factor
+    // The factor gradient (factor_grad.hip) runs the same program on the same scratch with kernels of its own; its array Gx
+    // lives behind `si` as well, fg_valid: Gx belongs to that factor.
     struct SelInv *si = nullptr ;
-    bool si_valid = false ;
+    bool si_valid = false, fg_valid = false ;
     int factor_state = 0 ;
     // gradients and the log-determinant (grad.hip): two panels, the partial sums, the column of every entry of the
     // resident S (built at the first call, void when S is uploaded anew) and the events live behind `gr`

@@ -11,26 +11,12 @@
 // things: the arena stays untouched (its slots are the factorization's, in any batch order), every square entry has one
 // writer by construction, and a batch may be cut into chunks anywhere.  The scratch is the squares of one chunk plus
 // one 64 x 64 partial per 64-row slice of its fronts; thin fronts need none (LDS).  info [5] counts both buffers.
+//
+// The launch program built here (Builder), the scratch and the stream events are shared with the factor gradient
+// (factor_grad.hip, through selinv_internal.hip.h: sweep_ensure, sweep_release, sweep_enter, sweep_leave, sweep_info): it
+// runs the same steps with kernels of its own, on the engine stream like this sweep, so the scratch has one user at a time.
 #include "selinv_kernels.hip.h"
-#include "plan.hip.h"
-
-struct SelInv {
-    enum { THIN, FILL, BLOCK, DIAG, STORE } ;
-    struct Step { int kind ; i64 first ; int ntasks ; unsigned grid ; size_t lds ; } ;
-    std::vector<Step> steps ;
-    std::vector<SiTask> tasks ;
-    std::vector<SiSlot> slots ;
-    std::vector<i32> thin ;
-    i64 m_len = 0, p_len = 0 ;              // doubles of the square scratch and of the partials
-    double hot_flops = 0, all_flops = 0 ;
-    bool built = false ;
-    SiTask *d_tasks = nullptr ; SiSlot *d_slots = nullptr ; i32 *d_thin = nullptr ;
-    double *d_Zx = nullptr, *d_M = nullptr, *d_P = nullptr ;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr, ev0 = nullptr, ev1 = nullptr ;
-    bool time_pending = false ;
-    double seconds = 0 ;
-    long launches = 0 ;
-} ;
+#include "selinv_internal.hip.h"
 
 namespace {
 
@@ -165,20 +151,6 @@ struct Builder {
     }
 } ;
 
-// what every entry point refuses, before any device call
-static bool bad_plan (const cholmod_hip_plan *P)
-{
-    if (!P || P->host_only || P->world > 1) return true ;
-    if (P->flags & (CHOLMOD_HIP_CX_STORAGE | CHOLMOD_HIP_PHI_TWIN)) return true ;       // real factors only
-    return P->factor_state != 1 || !P->d_Lx ;       // no numeric factor on the device, or one that is not positive definite
-}
-
-static void drop_buffers (SelInv *S)
-{
-    for (void *d : {(void *) S->d_Zx, (void *) S->d_M, (void *) S->d_P}) if (d) (void) hipFree (d) ;
-    S->d_Zx = S->d_M = S->d_P = nullptr ;
-}
-
 // once per plan: the program, its task lists on the device, the events
 static int prepare (cholmod_hip_plan *P, SelInv *S)
 {
@@ -192,34 +164,12 @@ static int prepare (cholmod_hip_plan *P, SelInv *S)
     S->d_thin = dupload (S->thin, e) ; HIPCHK (e) ;
     HIPCHK (hipEventCreateWithFlags (&S->ev_in, hipEventDisableTiming)) ;
     HIPCHK (hipEventCreateWithFlags (&S->ev_out, hipEventDisableTiming)) ;
-    HIPCHK (hipEventCreate (&S->ev0)) ;
-    HIPCHK (hipEventCreate (&S->ev1)) ;
+    for (SweepClock *c : {&S->si_clock, &S->fg_clock})
+    {
+        HIPCHK (hipEventCreate (&c->ev0)) ;
+        HIPCHK (hipEventCreate (&c->ev1)) ;
+    }
     S->built = true ;
-    return CHOLMOD_HIP_OK ;
-}
-
-// the program (once per plan), the events, Zx and the scratch; nothing is allocated once they exist
-static int ensure (cholmod_hip_plan *P)
-{
-    if (!P->si) P->si = new (std::nothrow) SelInv ;
-    SelInv *S = P->si ;
-    if (!S) return CHOLMOD_HIP_OUT_OF_MEMORY ;
-    if (!S->built)
-    {
-        const int rc = prepare (P, S) ;
-        if (rc != CHOLMOD_HIP_OK) { selinv_free (P) ; return rc ; }
-    }
-    if (S->d_Zx) return CHOLMOD_HIP_OK ;
-    const i64 want [3] = {P->xsize, S->m_len, S->p_len} ;
-    double **into [3] = {&S->d_Zx, &S->d_M, &S->d_P} ;
-    for (int k = 0 ; k < 3 ; k++)
-    {
-        const hipError_t e = hipMalloc ((void **) into [k], (size_t) std::max<i64> (want [k], 1) * sizeof (double)) ;
-        if (e == hipSuccess) continue ;
-        (void) hipGetLastError () ;
-        drop_buffers (S) ;              // (the factor is untouched)
-        return e == hipErrorOutOfMemory ? CHOLMOD_HIP_OUT_OF_MEMORY : CHOLMOD_HIP_GPU_PROBLEM ;
-    }
     return CHOLMOD_HIP_OK ;
 }
 
@@ -251,19 +201,56 @@ static void run (cholmod_hip_plan *P, hipStream_t st)
                 break ;
         }
     }
-    S->launches = (long) S->steps.size () ;
+    S->si_clock.launches = (long) S->steps.size () ;
 }
 
-// the engine stream takes its place in the caller's order: behind what the caller has enqueued ...
-static int enter (cholmod_hip_plan *P, hipStream_t user)
+} // namespace
+
+int sweep_ensure (cholmod_hip_plan *P, double *SelInv::*result)
+{
+    if (!P->si) P->si = new (std::nothrow) SelInv ;
+    SelInv *S = P->si ;
+    if (!S) return CHOLMOD_HIP_OUT_OF_MEMORY ;
+    if (!S->built)
+    {
+        const int rc = prepare (P, S) ;
+        if (rc != CHOLMOD_HIP_OK) { selinv_free (P) ; return rc ; }
+    }
+    const i64 want [3] = {P->xsize, S->m_len, S->p_len} ;
+    double **into [3] = {&(S->*result), &S->d_M, &S->d_P} ;
+    bool mine [3] = {false, false, false} ;
+    for (int k = 0 ; k < 3 ; k++)
+    {
+        if (*into [k]) continue ;
+        const hipError_t e = hipMalloc ((void **) into [k], (size_t) std::max<i64> (want [k], 1) * sizeof (double)) ;
+        mine [k] = (e == hipSuccess) ;
+        if (e == hipSuccess) continue ;
+        (void) hipGetLastError () ;
+        *into [k] = nullptr ;
+        for (int q = 0 ; q < k ; q++) if (mine [q]) { (void) hipFree (*into [q]) ; *into [q] = nullptr ; }   // (the factor is untouched)
+        return e == hipErrorOutOfMemory ? CHOLMOD_HIP_OUT_OF_MEMORY : CHOLMOD_HIP_GPU_PROBLEM ;
+    }
+    return CHOLMOD_HIP_OK ;
+}
+
+void sweep_release (cholmod_hip_plan *P, double *SelInv::*result)
+{
+    SelInv *S = P->si ;
+    if (S->*result) (void) hipFree (S->*result) ;
+    S->*result = nullptr ;
+    if (S->d_Zx || S->d_Gx) return ;
+    for (void *d : {(void *) S->d_M, (void *) S->d_P}) if (d) (void) hipFree (d) ;
+    S->d_M = S->d_P = nullptr ;
+}
+
+int sweep_enter (cholmod_hip_plan *P, hipStream_t user)
 {
     HIPCHK (hipEventRecord (P->si->ev_in, user)) ;
     HIPCHK (hipStreamWaitEvent (P->stream, P->si->ev_in, 0)) ;
     return CHOLMOD_HIP_OK ;
 }
 
-// ... and ahead of what the caller enqueues next
-static int leave (cholmod_hip_plan *P, hipStream_t user)
+int sweep_leave (cholmod_hip_plan *P, hipStream_t user)
 {
     HIPCHK (hipGetLastError ()) ;
     HIPCHK (hipEventRecord (P->si->ev_out, P->stream)) ;
@@ -271,16 +258,31 @@ static int leave (cholmod_hip_plan *P, hipStream_t user)
     return CHOLMOD_HIP_OK ;
 }
 
-} // namespace
+void sweep_info (SelInv *S, SweepClock &c, double *out8)
+{
+    if (c.pending)
+    {
+        float ms = 0 ;
+        if (hipEventSynchronize (c.ev1) == hipSuccess && hipEventElapsedTime (&ms, c.ev0, c.ev1) == hipSuccess)
+            c.seconds = ms * 1e-3 ;
+        else (void) hipGetLastError () ;
+        c.pending = false ;
+    }
+    out8 [0] = c.seconds ;
+    out8 [1] = (double) c.launches ;
+    out8 [2] = S->hot_flops ;
+    out8 [3] = S->all_flops ;
+}
 
 void selinv_free (cholmod_hip_plan *P)
 {
     SelInv *S = P->si ;
-    P->si = nullptr ; P->si_valid = false ;
+    P->si = nullptr ; P->si_valid = P->fg_valid = false ;
     if (!S) return ;
-    drop_buffers (S) ;
-    for (void *d : {(void *) S->d_tasks, (void *) S->d_slots, (void *) S->d_thin}) if (d) (void) hipFree (d) ;
-    for (hipEvent_t e : {S->ev_in, S->ev_out, S->ev0, S->ev1}) if (e) (void) hipEventDestroy (e) ;
+    for (void *d : {(void *) S->d_Zx, (void *) S->d_Gx, (void *) S->d_tr, (void *) S->d_M, (void *) S->d_P, (void *) S->d_tasks,
+        (void *) S->d_slots, (void *) S->d_thin}) if (d) (void) hipFree (d) ;
+    for (hipEvent_t e : {S->ev_in, S->ev_out, S->si_clock.ev0, S->si_clock.ev1, S->fg_clock.ev0, S->fg_clock.ev1})
+        if (e) (void) hipEventDestroy (e) ;
     delete S ;
 }
 
@@ -296,17 +298,17 @@ extern "C" {
 
 int cholmod_hip_selinv_device (cholmod_hip_plan *P, void *stream)
 {
-    if (bad_plan (P)) return CHOLMOD_HIP_INVALID ;
-    SI_TRY (ensure (P)) ;
+    if (sweep_bad_plan (P)) return CHOLMOD_HIP_INVALID ;
+    SI_TRY (sweep_ensure (P, &SelInv::d_Zx)) ;
     SelInv *S = P->si ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
     P->si_valid = false ;
-    SI_TRY (enter (P, user)) ;
-    HIPCHK (hipEventRecord (S->ev0, st)) ;
+    SI_TRY (sweep_enter (P, user)) ;
+    HIPCHK (hipEventRecord (S->si_clock.ev0, st)) ;
     run (P, st) ;
-    HIPCHK (hipEventRecord (S->ev1, st)) ;
-    SI_TRY (leave (P, user)) ;
-    S->time_pending = true ;
+    HIPCHK (hipEventRecord (S->si_clock.ev1, st)) ;
+    SI_TRY (sweep_leave (P, user)) ;
+    S->si_clock.pending = true ;
     P->si_valid = true ;
     return CHOLMOD_HIP_OK ;
 }
@@ -314,7 +316,7 @@ int cholmod_hip_selinv_device (cholmod_hip_plan *P, void *stream)
 int cholmod_hip_selinv_gather_device (cholmod_hip_plan *P, double *dZvalues, int64_t nvalues, double *dDiag, int perm,
     void *stream)
 {
-    if (bad_plan (P) || !P->si_valid || !P->si || !P->si->d_Zx) return CHOLMOD_HIP_INVALID ;
+    if (sweep_bad_plan (P) || !P->si_valid || !P->si || !P->si->d_Zx) return CHOLMOD_HIP_INVALID ;
     if (dZvalues)
     {
         // the value map of the current resident packed S, and values that are given, not computed
@@ -325,7 +327,7 @@ int cholmod_hip_selinv_gather_device (cholmod_hip_plan *P, double *dZvalues, int
     if ((!dZvalues && !dDiag) || P->n == 0) return CHOLMOD_HIP_OK ;
     const i64 n = P->n ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    SI_TRY (enter (P, user)) ;
+    SI_TRY (sweep_enter (P, user)) ;
     const unsigned ncol = (unsigned) ((n + 255) / 256) ;
     if (dZvalues)
     {
@@ -337,12 +339,12 @@ int cholmod_hip_selinv_gather_device (cholmod_hip_plan *P, double *dZvalues, int
     if (dDiag)
         hipLaunchKernelGGL (k_si_gather_diag, dim3 (ncol), dim3 (256), 0, st, n, perm ? P->d_perm : nullptr, P->d_supermap,
             P->d_fr, P->si->d_Zx, dDiag) ;
-    return leave (P, user) ;
+    return sweep_leave (P, user) ;
 }
 
 int cholmod_hip_selinv_download (cholmod_hip_plan *P, double *Zx_host)
 {
-    if (bad_plan (P) || !Zx_host || !P->si_valid || !P->si || !P->si->d_Zx) return CHOLMOD_HIP_INVALID ;
+    if (sweep_bad_plan (P) || !Zx_host || !P->si_valid || !P->si || !P->si->d_Zx) return CHOLMOD_HIP_INVALID ;
     HIPCHK (hipStreamSynchronize (P->stream)) ;
     if (P->xsize > 0) HIPCHK (hipMemcpy (Zx_host, P->si->d_Zx, (size_t) P->xsize * sizeof (double), hipMemcpyDeviceToHost)) ;
     return CHOLMOD_HIP_OK ;
@@ -350,32 +352,21 @@ int cholmod_hip_selinv_download (cholmod_hip_plan *P, double *Zx_host)
 
 int cholmod_hip_selinv_release (cholmod_hip_plan *P)
 {
-    if (bad_plan (P)) return CHOLMOD_HIP_INVALID ;
+    if (sweep_bad_plan (P)) return CHOLMOD_HIP_INVALID ;
     P->si_valid = false ;
     if (!P->si) return CHOLMOD_HIP_OK ;
     HIPCHK (hipStreamSynchronize (P->stream)) ;
-    drop_buffers (P->si) ;
+    sweep_release (P, &SelInv::d_Zx) ;
     return CHOLMOD_HIP_OK ;
 }
 
 int cholmod_hip_selinv_info (cholmod_hip_plan *P, double *out8)
 {
-    if (bad_plan (P) || !out8) return CHOLMOD_HIP_INVALID ;
+    if (sweep_bad_plan (P) || !out8) return CHOLMOD_HIP_INVALID ;
     for (int k = 0 ; k < 8 ; k++) out8 [k] = 0 ;
     SelInv *S = P->si ;
     if (!S) return CHOLMOD_HIP_OK ;
-    if (S->time_pending)
-    {
-        float ms = 0 ;
-        if (hipEventSynchronize (S->ev1) == hipSuccess && hipEventElapsedTime (&ms, S->ev0, S->ev1) == hipSuccess)
-            S->seconds = ms * 1e-3 ;
-        else (void) hipGetLastError () ;
-        S->time_pending = false ;
-    }
-    out8 [0] = S->seconds ;
-    out8 [1] = (double) S->launches ;
-    out8 [2] = S->hot_flops ;
-    out8 [3] = S->all_flops ;
+    sweep_info (S, S->si_clock, out8) ;
     out8 [4] = S->d_Zx ? 8.0 * (double) std::max<i64> (P->xsize, 1) : 0.0 ;
     out8 [5] = S->d_Zx ? 8.0 * (double) (std::max<i64> (S->m_len, 1) + std::max<i64> (S->p_len, 1)) : 0.0 ;
     out8 [6] = P->si_valid ? 1.0 : 0.0 ;
