@@ -329,8 +329,11 @@ __global__ void __launch_bounds__(256) k_extend_add (const EaGroup *g, int ng,
 // Both results are within 1 ulp for normal d.
 // Branch-free: arguments outside [1e-290, 1e290] are rescaled by 2^(+-512)
 // around the iteration (v_ldexp_f64), so there is no slow path for hipcc to
-// if-convert onto the caller's dependency chain.  d <= 0 or non-finite gives
-// NaN / garbage, which every caller masks (a failed pivot).
+// if-convert onto the caller's dependency chain.  d <= 0 gives NaN / garbage,
+// which every caller masks (a failed pivot).  A NaN or +Inf pivot is NOT a
+// failed pivot and nobody masks it: NaN gives NaN, as the reference's sqrt;
+// +Inf gives NaN too (rsq (inf) = 0, g = inf * 0), where the reference has
+// L (j,j) = +inf and zeros below it (tests/nonfinite_cases.py).
 __device__ __forceinline__ void sqrt_rsqrt (double d, double &r, double &ri)
 {
     int sh = d > 1e290 ? -512 : (d < 1e-290 ? 512 : 0) ;
