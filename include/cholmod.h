@@ -457,6 +457,35 @@ int cholmod_l_hip_selinv_device (cholmod_sparse *A, cholmod_factor *L, double *Z
  * (Z (s [pi [k] + i], super [k] + j), i >= j, at px [k] + i + j nsrow; zeros above the diagonal of the diagonal blocks), in
  * the factor's ordering.  Computes the inverse if it is stale and waits for it.  Refusals as above. */
 int cholmod_l_hip_selinv_to_host (cholmod_factor *L, double *Zx, cholmod_common *Common) ;
+/* The Schur complement onto a set S of m variables and the two condensed solves that go with it (csrc/host/schur.c), for
+ * the A and beta L was last factorized from ON THE DEVICE.  S is the LAST m positions of the factor's ordering:
+ *     row i of Sc, F, G and XS is variable L->Perm [n - m + i] of the caller's matrix
+ * -- that is the contract.  With a nested-dissection ordering these are the top separators; to condense onto a chosen set,
+ * order it last (analyze with a permutation that ends with it, Common->postorder = FALSE).  Any m may be chosen after the
+ * factorization, and several from one factor; the factorization itself is not touched.  With I the other n - m variables:
+ * cholmod_l_hip_schur_device: S_dev (NULL, or m-by-m doubles on the device, column-major, lds >= m) receives
+ *     Sc = (A + beta I)_SS - (A + beta I)_SI inv ((A + beta I)_II) (A + beta I)_IS,
+ * both triangles, bitwise symmetric -- the marginal precision of x_S of a Gaussian Markov random field, the interface matrix
+ * of a substructure; F_dev (NULL, or m-by-m, ldf >= m) its Cholesky factor, Sc = F F': the trailing triangle of L, dense,
+ * exact +0.0 above the diagonal.  Not both NULL.  The same factor gives the same bits.
+ * cholmod_l_hip_schur_reduce_device: B_dev (n-by-nrhs, column-major, ldb >= n, the caller's ordering, read only); Y_dev
+ * (n-by-nrhs, ldy >= n) receives inv (L) P B in the FACTOR's ordering, which the caller keeps for the expansion; G_dev
+ * (m-by-nrhs, ldg >= m) receives the condensed right-hand side B_S - (A + beta I)_SI inv ((A + beta I)_II) B_I.
+ * cholmod_l_hip_schur_expand_device: XS_dev (m-by-nrhs, ldxs >= m, read only) is the solution on S -- of Sc x_S = G, or of
+ * whatever the caller has added to both --; Y_dev is what the reduction left, read only; X_dev (n-by-nrhs, ldx >= n, not
+ * Y_dev, not overlapping XS_dev) receives the solution on all variables in the caller's ordering: x_S on S, and
+ * inv ((A + beta I)_II) (B_I - (A + beta I)_IS x_S) on I.  With m == 0 it is the plain solve P' inv (L') Y.
+ * All three take their place on `stream` as cholmod_l_hip_solve_device does; the host does not wait once the workspaces
+ * exist.  m == 0 (but for the expansion) or nrhs == 0: success, nothing touched.
+ * FALSE with CHOLMOD_INVALID for a NULL L or array, m > n, a leading dimension too small, a symbolic or simplicial L,
+ * L->minor < n, the GPU switched off (no host fallback: Common->hip_cpu_fallback does not apply), several ranks, an L not
+ * factorized on the device; with CHOLMOD_NOT_INSTALLED for a complex or zomplex L -- all before a device is touched. */
+int cholmod_l_hip_schur_device (cholmod_factor *L, size_t m, double *S_dev, size_t lds, double *F_dev, size_t ldf,
+    void *stream, cholmod_common *Common) ;
+int cholmod_l_hip_schur_reduce_device (cholmod_factor *L, size_t m, const double *B_dev, size_t ldb, double *Y_dev, size_t ldy,
+    double *G_dev, size_t ldg, size_t nrhs, void *stream, cholmod_common *Common) ;
+int cholmod_l_hip_schur_expand_device (cholmod_factor *L, size_t m, const double *Y_dev, size_t ldy, const double *XS_dev,
+    size_t ldxs, double *X_dev, size_t ldx, size_t nrhs, void *stream, cholmod_common *Common) ;
 /* What backpropagation through the device path needs (csrc/host/grad.c; suitesparse_amd/autograd.py ties them into
  * torch.autograd.Functions).  cholmod_l_hip_values_grad_device: G_dev (nnz (A) doubles on the device, A's entry order)
  * receives, for every entry (i, j) of A the factorization reads,

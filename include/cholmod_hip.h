@@ -428,6 +428,37 @@ int cholmod_hip_selinv_release (cholmod_hip_plan *plan) ;
  * scratch  [6] 1 if Zx is current  [7] reserved, zero */
 int cholmod_hip_selinv_info (cholmod_hip_plan *plan, double *out8) ;
 
+/* (This entry point and the next: csrc/hip/schur.hip.)
+ * The Schur complement onto the LAST m variables of the factor's ordering.  With L the resident factor of
+ * P (A + beta I) P', I its first n - m positions and S its last m,  L = [L11 0 ; L21 L22]  and
+ *     Sc = (A + beta I)_SS - (A + beta I)_SI inv ((A + beta I)_II) (A + beta I)_IS = L22 L22',
+ * so that L22 is the Cholesky factor of Sc.  Row i of Sc and of L22 is position n - m + i of the factor's ordering.  Any m
+ * may be chosen after the factorization, and several from one factor; the factorization and its schedule are untouched.
+ * dS: Sc, m-by-m, column-major, lds >= m, BOTH triangles written, bitwise symmetric.  dF: the dense L22, m-by-m,
+ * column-major, ldf >= m: lower triangle = L (n-m+i, n-m+j), strict upper = +0.0; entries of L outside its pattern = +0.0.
+ * Either pointer may be NULL, not both.  Nothing outside the m-by-m arrays is written.  0 <= m <= n; m == 0 is a success
+ * that touches nothing.
+ * One workgroup owns one 64 x 64 tile of the lower triangle of Sc and walks the supernodes that hold trailing columns in
+ * ascending order, on v_mfma_f64_16x16x4; the strictly upper triangle of every diagonal block counts as zero whatever Lx
+ * holds there.  One owner and one summation order, no floating-point atomics: two calls give the same bits.  The work is
+ * the sum over the trailing supernodes of (rows from the first trailing column down)^2 x (trailing columns) multiply-adds,
+ * at most about m^3 / 3.
+ * Ordered on `stream` exactly as the selected inverse is: the engine stream waits for an event recorded on it, `stream`
+ * waits for the engine's completion event; the first call creates the two events, after that nothing is allocated and the
+ * host does not wait.  No host-device copy.  Not during capture.
+ * CHOLMOD_HIP_INVALID, before any device call, for a NULL plan, a host-only plan, several ranks, the plan of a complex factor,
+ * no positive definite numeric factor on the device, m < 0 or m > n, a leading dimension < m, both outputs NULL. */
+int cholmod_hip_schur_device (cholmod_hip_plan *plan, int64_t m, double *dS, int64_t lds, double *dF, int64_t ldf,
+    void *stream) ;
+/* dOut (m-by-nrhs, column-major, ldo >= m) = L22 dV (trans = 0) or L22' dV (trans = 1), dV m-by-nrhs, ldv >= m, read only;
+ * dOut != dV.  With the L and L' sweeps of the device solve these give the condensed right-hand side (L22 times the last m
+ * rows of inv (L) P b) and the back-expansion.  L22' dV: one owner per row of dOut and a fixed summation tree, the same
+ * inputs give the same bits.  L22 dV: the columns add into the cleared dOut atomically, as the forward solve does into
+ * its right-hand side: the result is reproducible to rounding only.  Ordered on `stream` as above.  CHOLMOD_HIP_INVALID as
+ * above and for a NULL array, nrhs < 0, dOut == dV; m == 0 or nrhs == 0 is a success that touches nothing. */
+int cholmod_hip_trailing_multiply_device (cholmod_hip_plan *plan, int64_t m, int trans, const double *dV, int64_t ldv,
+    double *dOut, int64_t ldo, int64_t nrhs, void *stream) ;
+
 /* (This entry point and the five after it: csrc/hip/factor_grad.hip.)
  * The gradient through the factor (reverse-mode Cholesky): given Lbar = df/dL on the pattern of L, Gx = df/dS on the
  * pattern of L, where S = L L' = P (A + beta I) P' is LOWER-STORED -- an off-diagonal entry stands for two entries of the

@@ -151,6 +151,7 @@ API_SYMBOLS = [
     "cholmod_l_hip_solve_device_complex", "cholmod_l_hip_residual_device_complex", "cholmod_l_hip_refine_device_complex",
     "cholmod_l_hip_factorize_values_device", "cholmod_l_hip_aat_product_map",
     "cholmod_l_hip_selinv_device", "cholmod_l_hip_selinv_to_host",
+    "cholmod_l_hip_schur_device", "cholmod_l_hip_schur_reduce_device", "cholmod_l_hip_schur_expand_device",
     "cholmod_l_hip_values_grad_device", "cholmod_l_hip_logdet_device",
     "cholmod_l_hip_aat_values_grad_device", "cholmod_l_hip_aat_logdet_grad_device",
     "cholmod_l_hip_factor_grad_device", "cholmod_l_hip_factor_outer_grad_device", "cholmod_l_hip_factor_grad_to_host",
@@ -169,6 +170,7 @@ HIP_SYMBOLS = [
     "cholmod_hip_get_maps", "cholmod_hip_get_stats", "cholmod_hip_set_profiling",
     "cholmod_hip_selinv_device", "cholmod_hip_selinv_gather_device", "cholmod_hip_selinv_download",
     "cholmod_hip_selinv_release", "cholmod_hip_selinv_info",
+    "cholmod_hip_schur_device", "cholmod_hip_trailing_multiply_device",
     "cholmod_hip_factor_grad_device", "cholmod_hip_factor_outer_grad_device", "cholmod_hip_factor_grad_gather_device",
     "cholmod_hip_factor_grad_download", "cholmod_hip_factor_grad_release", "cholmod_hip_factor_grad_info",
     "cholmod_hip_values_grad_device", "cholmod_hip_logdet_device",
@@ -322,6 +324,11 @@ def lib(hooks=None):
     sig("cholmod_hip_selinv_info", C.c_int, [vp, vp])
     sig("cholmod_l_hip_selinv_device", C.c_int, [sp, fc, vp, vp, vp, cm])
     sig("cholmod_l_hip_selinv_to_host", C.c_int, [fc, vp, cm])
+    sig("cholmod_hip_schur_device", C.c_int, [vp, i64, vp, i64, vp, i64, vp])
+    sig("cholmod_hip_trailing_multiply_device", C.c_int, [vp, i64, C.c_int, vp, i64, vp, i64, i64, vp])
+    sig("cholmod_l_hip_schur_device", C.c_int, [fc, sz, vp, sz, vp, sz, vp, cm])
+    sig("cholmod_l_hip_schur_reduce_device", C.c_int, [fc, sz, vp, sz, vp, sz, vp, sz, sz, vp, cm])
+    sig("cholmod_l_hip_schur_expand_device", C.c_int, [fc, sz, vp, sz, vp, sz, vp, sz, sz, vp, cm])
     sig("cholmod_hip_factor_grad_device", C.c_int, [vp, vp, vp])
     sig("cholmod_hip_factor_outer_grad_device", C.c_int, [vp, dbl, vp, i64, vp, i64, i64, vp])
     sig("cholmod_hip_factor_grad_gather_device", C.c_int, [vp, vp, i64, vp, vp])
@@ -815,6 +822,184 @@ class Session:
         if not self.L.cholmod_l_hip_factor_grad_to_host(Lf, out.ctypes.data, C.byref(self.cm)):
             raise RuntimeError(f"cholmod_l_hip_factor_grad_to_host failed, status {self.cm.status}")
         return out[:int(Lf.contents.xsize)]
+
+    # ---- the Schur complement onto the last m variables of the factor's ordering
+    @staticmethod
+    def schur_index(Lf, m):
+        """The variables of A the rows of `schur_device`, of G and of XS stand for: Perm [n - m:], as an np.int64 array."""
+        f = Lf.contents
+        n, m = int(f.n), int(m)
+        if not 0 <= m <= n:
+            raise ValueError(f"schur_index: m must lie in 0 .. n = {n}")
+        return _view(f.Perm, n, C.c_int64, np.int64)[n - m:].copy()
+
+    @staticmethod
+    def _square_layout(what, m, t, dev):
+        """leading dimension of the (m, m) torch.float64 device tensor t: unit stride along a row, row stride >= m"""
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.device == dev):
+            raise ValueError(f"{what} must be a torch.float64 tensor on the current device")
+        if t.dim() != 2 or tuple(t.shape) != (m, m) or (m > 1 and (t.stride(1) != 1 or t.stride(0) < m)):
+            raise ValueError(f"{what} must have shape ({m}, {m}), unit stride along a row and a row stride >= {m}")
+        return int(t.stride(0)) if m > 1 else max(m, 1)
+
+    def schur_device(self, Lf, m=None, subset=None, factor=False, out=None):
+        """cholmod_l_hip_schur_device: the Schur complement Sc of the matrix Lf was last factorized from on the device (plus
+        beta I) onto the LAST m variables of the factor's ordering -- the variables `schur_index (Lf, m)` of A, in that
+        order -- as an (m, m) torch.float64 device tensor, both triangles, bitwise symmetric.  factor=True: (Sc, F) with
+        F [i, j] = L22 (i, j), the Cholesky factor of Sc (F @ F.T is Sc; torch.cholesky_solve (g, F) solves with it): a
+        transposed view of the column-major array, exact +0.0 above the diagonal.  subset: a sequence of distinct
+        variables of A instead of m; it must be the set of the last len (subset) variables of the factor's ordering (see
+        `schur_perm`), and rows and columns come back in ITS order.  out: a tensor for Sc, or with factor=True a pair
+        (tensor for Sc, tensor for the column-major array behind F); shape (m, m), unit stride along a row, any row
+        stride >= m -- nothing outside the (m, m) block is written; not with subset.  Enqueued on torch's current stream;
+        the same factor gives the same bits."""
+        import torch
+        n = int(Lf.contents.n)
+        order = None
+        if subset is not None:
+            sub = np.asarray(subset, dtype=np.int64).reshape(-1)
+            if m is not None and int(m) != len(sub):
+                raise ValueError("schur_device: m and len (subset) differ")
+            if out is not None:
+                raise ValueError("schur_device: out cannot be combined with subset")
+            m = len(sub)
+            if m > n or len(set(sub.tolist())) != m or (m and (sub.min() < 0 or sub.max() >= n)):
+                raise ValueError("schur_device: subset must hold distinct variables 0 .. n-1 of A")
+            tail = self.schur_index(Lf, m)
+            if set(tail.tolist()) != set(sub.tolist()):
+                raise ValueError("schur_device: subset is not the set of the last len (subset) variables of the factor's "
+                                 "ordering; analyze with schur_perm (A, subset) on a Session with postorder=False (the "
+                                 "weighted postorder may move a variable of the subset)")
+            pos = {int(v): k for k, v in enumerate(tail)}
+            order = np.array([pos[int(v)] for v in sub], dtype=np.int64)
+        if m is None:
+            raise ValueError("schur_device: m or subset is needed")
+        m = int(m)
+        if not 0 <= m <= n:
+            raise ValueError(f"schur_device: m must lie in 0 .. n = {n}")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        So, Fo = (out if isinstance(out, (tuple, list)) else (out, None)) if out is not None else (None, None)
+        Sc = torch.empty((m, m), dtype=torch.float64, device=dev) if So is None else So
+        lds = self._square_layout("schur_device: out", m, Sc, dev)
+        Fb, ldf = None, max(m, 1)
+        if factor:
+            Fb = torch.empty((m, m), dtype=torch.float64, device=dev) if Fo is None else Fo
+            ldf = self._square_layout("schur_device: out [1]", m, Fb, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ok = self.L.cholmod_l_hip_schur_device(Lf, m, Sc.data_ptr() or 1, lds, (Fb.data_ptr() or 2) if factor else None, ldf,
+                                               stream, C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_schur_device failed, status {self.cm.status}")
+        F = Fb.t() if factor else None
+        if order is not None:
+            idx = torch.as_tensor(order, device=dev)
+            Sc = Sc.index_select(0, idx).index_select(1, idx)
+            # (a symmetric permutation of L22 is not triangular: with subset, F stays in the factor's order)
+        return (Sc, F) if factor else Sc
+
+    def schur_reduce_device(self, Lf, m, B):
+        """cholmod_l_hip_schur_reduce_device: the condensed right-hand side.  B: device tensor as for `solve_device`, shape
+        (nrhs, n) or (n,), in A's ordering.  Returns (G, Y): G of shape (nrhs, m) (or (m,)), B_S - A_SI inv (A_II) B_I for
+        S = `schur_index (Lf, m)`; Y of the shape of B, inv (L) P B in the factor's ordering, for `schur_expand_device`.
+        Enqueued on torch's current stream."""
+        import torch
+        n, m = int(Lf.contents.n), int(m)
+        if not 0 <= m <= n:
+            raise ValueError(f"schur_reduce_device: m must lie in 0 .. n = {n}")
+        ldb, nrhs = self._device_layout("schur_reduce_device: B", n, B)
+        Y = torch.empty(B.shape, dtype=torch.float64, device=B.device)
+        G = torch.empty(B.shape[:-1] + (m,), dtype=torch.float64, device=B.device)
+        stream = torch.cuda.current_stream(B.device).cuda_stream
+        ok = self.L.cholmod_l_hip_schur_reduce_device(Lf, m, B.data_ptr() or 1, ldb, Y.data_ptr() or 2, n, G.data_ptr() or 3,
+                                                      max(m, 1), nrhs, stream, C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_schur_reduce_device failed, status {self.cm.status}")
+        return G, Y
+
+    def schur_expand_device(self, Lf, m, Y, XS, out=None):
+        """cholmod_l_hip_schur_expand_device: the solution on all variables from the solution XS on S = `schur_index (Lf,
+        m)` (shape (nrhs, m) or (m,), of Sc x_S = G or of what the caller has added to both) and the Y of
+        `schur_reduce_device` (read only).  Returns X of the shape of Y in A's ordering, or writes into `out` (never Y).
+        m = 0: the plain solve P' inv (L') Y.  Enqueued on torch's current stream."""
+        import torch
+        n, m = int(Lf.contents.n), int(m)
+        if not 0 <= m <= n:
+            raise ValueError(f"schur_expand_device: m must lie in 0 .. n = {n}")
+        ldy, nrhs = self._device_layout("schur_expand_device: Y", n, Y)
+        if not (isinstance(XS, torch.Tensor) and XS.dim() == Y.dim() and XS.shape[:-1] == Y.shape[:-1]):
+            raise ValueError("schur_expand_device: XS must have one right-hand side per right-hand side of Y")
+        ldxs, _ = self._device_layout("schur_expand_device: XS", m, XS)
+        if XS.device != Y.device:
+            raise ValueError("schur_expand_device: XS must be on the device of Y")
+        if out is None:
+            out = torch.empty(Y.shape, dtype=torch.float64, device=Y.device)
+        ldx, _ = self._device_layout("schur_expand_device: out", n, out, like=Y)
+        stream = torch.cuda.current_stream(Y.device).cuda_stream
+        ok = self.L.cholmod_l_hip_schur_expand_device(Lf, m, Y.data_ptr() or 2, ldy, XS.data_ptr() or 3, max(ldxs, 1),
+                                                      out.data_ptr() or 1, ldx, nrhs, stream, C.byref(self.cm))
+        if not ok:
+            raise RuntimeError(f"cholmod_l_hip_schur_expand_device failed, status {self.cm.status}")
+        return out
+
+    @staticmethod
+    def schur_perm(A, subset):
+        """A permutation for `analyze` that orders `subset` (distinct variables of A) LAST, in the given order: the
+        built-in fill-reducing ordering of the principal submatrix of A on the other variables (for an unsymmetric A,
+        stype 0, whose A A' is factorized: of its rows), then subset.  Analyze with it on a Session with postorder=False:
+        the weighted postorder may move a variable of the subset.  A pure host helper: the submatrix's pattern is analyzed
+        on the host and its Perm read."""
+        a = A.contents
+        n = int(a.nrow)
+        sub = np.asarray(subset, dtype=np.int64).reshape(-1)
+        if len(sub) and (sub.min() < 0 or sub.max() >= n):
+            raise ValueError("schur_perm: subset holds a variable outside 0 .. n-1")
+        if len(set(sub.tolist())) != len(sub):
+            raise ValueError("schur_perm: subset holds a variable twice")
+        keep = np.ones(n, dtype=bool)
+        keep[sub] = False
+        rest = np.flatnonzero(keep).astype(np.int64)
+        if len(rest) == 0:
+            return sub.copy()
+        ncol = int(a.ncol)
+        Ap = _view(a.p, ncol + 1, C.c_int64, np.int64)
+        if a.packed:
+            cnt = np.diff(Ap)
+        else:
+            cnt = _view(a.nz, ncol, C.c_int64, np.int64)
+        col = np.repeat(np.arange(ncol, dtype=np.int64), cnt)
+        pos = np.concatenate([np.arange(Ap[j], Ap[j] + cnt[j], dtype=np.int64) for j in range(ncol)]) if ncol else np.zeros(0, np.int64)
+        row = _view(a.i, max(int(Ap[-1]), 1), C.c_int64, np.int64)[pos] if len(pos) else np.zeros(0, np.int64)
+        newid = np.full(n, -1, dtype=np.int64)
+        newid[rest] = np.arange(len(rest))
+        if a.stype != 0:
+            ok = keep[row] & keep[col]
+            r, c, nc = newid[row[ok]], newid[col[ok]], len(rest)
+        else:
+            ok = keep[row]
+            r, c, nc = newid[row[ok]], col[ok], ncol
+        o = np.lexsort((r, c))
+        r, c = r[o], c[o]
+        Bp = np.zeros(nc + 1, dtype=np.int64)
+        np.add.at(Bp, c + 1, 1)
+        Bp = np.cumsum(Bp)
+        S = Session(use_gpu=0, ordering="default")
+        nzb = max(int(Bp[-1]), 1)
+        Bm = S.L.cholmod_l_allocate_sparse(len(rest), nc, nzb, 1, 1, int(a.stype), REAL, C.byref(S.cm))
+        if not Bm:
+            raise MemoryError("cholmod_l_allocate_sparse")
+        _view(Bm.contents.p, nc + 1, C.c_int64, np.int64)[:] = Bp
+        if len(r):
+            _view(Bm.contents.i, len(r), C.c_int64, np.int64)[:] = r
+            _view(Bm.contents.x, len(r), C.c_double, np.float64)[:] = 1.0
+        try:
+            Lf = S.analyze(Bm)
+            head = _view(Lf.contents.Perm, len(rest), C.c_int64, np.int64).copy()
+            S.free_factor(Lf)
+        finally:
+            S.free_sparse(Bm)
+            S.finish()
+        return np.concatenate([rest[head], sub])
 
     def solve_subset(self, Lf, b, bset, sys=SYS_A, handles=None):
         """cholmod_l_solve2 with a sparse right-hand side: b (length n, only its entries at the indices `bset` are

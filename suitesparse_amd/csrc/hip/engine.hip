@@ -47,7 +47,7 @@ static void free_device (cholmod_hip_plan *P)
     if (P->stream2) (void) hipStreamDestroy (P->stream2) ;
     if (P->ev0) (void) hipEventDestroy (P->ev0) ;
     if (P->ev1) (void) hipEventDestroy (P->ev1) ;
-    for (hipEvent_t e : {P->sd_ev_in, P->sd_ev0, P->sd_ev1, P->rs_ev_out}) if (e) (void) hipEventDestroy (e) ;
+    for (hipEvent_t e : {P->sd_ev_in, P->sd_ev0, P->sd_ev1, P->rs_ev_out, P->sc_ev_in, P->sc_ev_out}) if (e) (void) hipEventDestroy (e) ;
     if (P->stream) (void) hipStreamDestroy (P->stream) ;
 }
 

@@ -408,6 +408,9 @@ struct cholmod_hip_plan {
     struct SelInv *si = nullptr ;
     bool si_valid = false, fg_valid = false ;
     int factor_state = 0 ;
+    // Schur complement and trailing multiplies (schur.hip): the event the engine stream waits for on the caller's stream
+    // and the one the caller's stream waits for (created by the first call)
+    hipEvent_t sc_ev_in = nullptr, sc_ev_out = nullptr ;
     // gradients and the log-determinant (grad.hip): two panels, the partial sums, the column of every entry of the
     // resident S (built at the first call, void when S is uploaded anew) and the events live behind `gr`
     struct Grad *gr = nullptr ;
