@@ -1,9 +1,11 @@
 """The device fuzz, run in a process of its own (tests/test_gpu_device_fuzz.py): `python device_fuzz_runner.py SEED NCASE`,
 torch imported FIRST (see solve_device_cases.py).  Every case of tests/device_fuzz_corpus.py goes through the
 device-resident features -- factorization, solves, residual and refinement, selected inverse, log-determinant, the
-gradients with respect to the values and through L, refactorization from device values, the scratch budget, the complex
-solves, the gradients through A A' + beta I -- and every result is compared with a dense float64 numpy / scipy / torch-CPU
-reference on P (A + beta I) P', P the factor's own Perm, at the bar the project already holds that feature to (named where
+gradients with respect to the values and through L, the Schur complement and the condensed solves (for the m of
+device_fuzz_corpus.schur_ms, interleaved with the sweeps, the solves and the refactorization on the one plan),
+refactorization from device values, the scratch budget, the complex solves, the complex block arrows with L judged by
+supernode, the gradients through A A' + beta I and the Schur complement of that factor -- and every result is compared
+with a dense float64 numpy / scipy / torch-CPU reference on P (A + beta I) P', P the factor's own Perm, at the bar the project already holds that feature to (named where
 it is used).  The launches both sweeps report must be those of the launch program restated in device_fuzz_corpus.sweep_program:
 a front that takes another kernel path than the class map says shows there even where both paths compute the same numbers.
 
@@ -34,9 +36,11 @@ import factor_grad_reference as F
 import grad_reference as GR
 import selinv_reference as R
 import residual_device_cases as RD
+import schur_reference as SR
 import solve_device_complex_cases as CX
 from factor_grad_cases import _compare as _grad_compare
 from grad_cases import _diag_of
+from schur_cases import _multiply, _padded, _untouched
 from selinv_cases import _entry_positions
 from solve_device_cases import TOL as TOL_SOLVE, _relcols
 from suitesparse_amd import cholmod as ch
@@ -47,7 +51,7 @@ TOL_REFINE = 1e-11      # the relative residual after one step (solve_device_com
 TOL_LOGDET = 1e-11      # relative to sum |2 log L_jj| (grad_cases.case_autograd, aat_grad_cases.case_autograd)
 BUDGET = "CHOLMOD_HIP_SELINV_BUDGET_MB"
 FEATURES = ("factor", "solve", "residual_refine", "selinv", "logdet", "values_grad", "factor_grad", "outer_grad",
-            "factorize_device", "budget_bits", "complex_solve", "aat")
+            "factorize_device", "budget_bits", "complex_solve", "aat", "schur", "schur_condensed", "complex_arrow")
 EXIT_HIP_ERROR = 3
 
 
@@ -117,11 +121,90 @@ def _permuted(Ad, fv):
     return Ad[np.ix_(p, p)]
 
 
-def _check_factor(book, feature, fv, Lref):
-    """L against the dense Cholesky factor at TOL_L (Frobenius), the dead triangles exact zeros"""
+def _check_factor(book, feature, fv, Lref, by_supernode=False):
+    """L against the dense Cholesky factor at TOL_L (Frobenius), the dead triangles exact zeros; by_supernode (the block
+    arrows): L by supernode at TOL_L as well, a wrong leaf that the norm over the whole factor would drown"""
     _, mask = F.trapezoid_of(np.zeros((fv.n, fv.n)), fv.super, fv.pi, fv.px, fv.s, fv.xsize)
     book.check(feature, "L", np.linalg.norm(F.dense_factor(fv) - Lref) / np.linalg.norm(Lref), TOL_L)
     book.check(feature, "dead triangles of L", np.count_nonzero(fv.x[~mask] != 0.0), 0)
+    if by_supernode:
+        _check_by_supernode(book, feature, fv, Lref)
+
+
+def _check_by_supernode(book, feature, fv, Lref):
+    """max |L - L_ref| over a supernode / max |L_ref| of it, the worst supernode, at TOL_L (not_posdef_cases.by_entry)"""
+    worst, k, dead, imag = DC.by_supernode(fv, fv.x, Lref)
+    shape = (int(fv.super[k + 1] - fv.super[k]), int(fv.pi[k + 1] - fv.pi[k])) if k >= 0 else None
+    book.check(feature, f"L by supernode, the worst: supernode {k}, nscol x nsrow {shape}", worst, TOL_L)
+    return dead, imag
+
+
+def _check_schur(book, S, Lf, fv, Mp, ms, n):
+    """schur_device (factor=True) for every m of ms into poisoned, over-allocated buffers: Sc against the dense Schur
+    complement of Mp = P (A + beta I) P' (m = n: Mp itself) at the bar of schur_cases, relative to max |ref|; Sc bitwise
+    symmetric; nothing written outside the two m x m corners; F bit for bit schur_reference.trailing_factor of the
+    downloaded factor; a second call, into fresh tensors, gives the same bits -> {m: (Sc, F)}"""
+    fac, tol = (fv.super, fv.pi, fv.px, fv.s, fv.x), R.tolerance(R.factor_rcond(fv))
+    got = {}
+    for m in ms:
+        sbuf, sview = _padded(m)
+        fbuf, fview = _padded(m)
+        Sc, Fm = S.schur_device(Lf, m, factor=True, out=(sview, fview))
+        torch.cuda.synchronize()
+        _guard(S)
+        book.check("schur", f"m {m}: entries written outside the m x m corners", int(not (_untouched(sbuf, m) and _untouched(fbuf, m))), 0)
+        Sh, Fh = Sc.cpu().numpy(), Fm.cpu().numpy()
+        ref = SR.dense_schur(Mp, m)
+        with np.errstate(invalid="ignore"):
+            book.check("schur", f"Sc m {m}" + (" = n, the permuted matrix itself" if m == n else ""),
+                       np.abs(Sh - ref).max() / np.abs(ref).max(), tol)
+        book.check("schur", f"Sc m {m} symmetric, bits", np.count_nonzero(_bits(Sh) != _bits(Sh.T)), 0)
+        book.check("schur", f"F m {m}, bits", np.count_nonzero(_bits(Fh) != _bits(SR.trailing_factor(*fac, n, m))), 0)
+        S2, F2 = S.schur_device(Lf, m, factor=True)
+        book.check("schur", f"Sc m {m} twice, bits", np.count_nonzero(_bits(S2.cpu().numpy()) != _bits(Sh)), 0)
+        book.check("schur", f"F m {m} twice, bits", np.count_nonzero(_bits(F2.cpu().numpy()) != _bits(Fh)), 0)
+        _guard(S)
+        got[m] = (Sh, Fh)
+    return got
+
+
+def _check_condensed(book, S, Lf, fv, Ad, Mp, got, ms, nrhs_list, rng):
+    """reduce, the interface solve on the host with F, expand, for the first and the last m and the smallest and the largest
+    nrhs: G against schur_reference.dense_reduce at the bar; X against the dense solve at solve_device_cases.TOL per column;
+    X on schur_index against x_S at the bar; Y the same bits after the expansion AND after a solve_device call on other
+    right-hand sides in between (the sweeps share the engine's panel).  The two trailing products against numpy at the bar,
+    L22' V twice with the same bits."""
+    n, P, tol = fv.n, np.asarray(fv.Perm), R.tolerance(R.factor_rcond(fv))
+    for m in dict.fromkeys((ms[0], ms[-1])):
+        Fh = got[m][1]
+        idx = S.schur_index(Lf, m)
+        book.check("schur_condensed", f"schur_index m {m}", np.count_nonzero(idx != P[n - m:]), 0)
+        for nrhs in dict.fromkeys((nrhs_list[0], nrhs_list[-1])):
+            b, other = rng.standard_normal((nrhs, n)), rng.standard_normal((nrhs, n))
+            B = _dev(b)
+            G, Y = S.schur_reduce_device(Lf, m, B)
+            Gh, Y0 = G.cpu().numpy(), Y.clone()
+            _guard(S)
+            Gref = SR.dense_reduce(Mp, m, b[:, P].T).T
+            book.check("schur_condensed", f"G m {m} nrhs {nrhs}", np.abs(Gh - Gref).max() / np.abs(Gref).max(), tol)
+            xS = sla.cho_solve((Fh, True), Gh.T).T
+            xo = S.solve_device(Lf, _dev(other)).cpu().numpy()
+            book.check("schur_condensed", f"solve_device between reduce and expand, nrhs {nrhs}",
+                       _relcols(xo, np.linalg.solve(Ad, other.T).T), TOL_SOLVE)
+            X = S.schur_expand_device(Lf, m, Y, _dev(xS)).cpu().numpy()
+            _guard(S)
+            book.check("schur_condensed", f"Y m {m} nrhs {nrhs} unchanged, bits",
+                       int((Y.view(torch.int64) != Y0.view(torch.int64)).sum()), 0)
+            book.check("schur_condensed", f"X m {m} nrhs {nrhs}", _relcols(X, np.linalg.solve(Ad, b.T).T), TOL_SOLVE)
+            book.check("schur_condensed", f"X on schur_index against x_S, m {m} nrhs {nrhs}",
+                       np.abs(X[:, idx] - xS).max() / np.abs(xS).max(), tol)
+        v = rng.standard_normal((nrhs_list[-1], m))
+        V = _dev(v)
+        t1, t2, n1 = _multiply(S, Lf, m, 1, V), _multiply(S, Lf, m, 1, V), _multiply(S, Lf, m, 0, V)
+        _guard(S)
+        book.check("schur_condensed", f"L22' V twice, m {m}, bits", int((t1.view(torch.int64) != t2.view(torch.int64)).sum()), 0)
+        for name, out, want in (("L22' V", t1, v @ Fh), ("L22 V", n1, v @ Fh.T)):
+            book.check("schur_condensed", f"{name} m {m}", np.abs(out.cpu().numpy() - want).max() / np.abs(want).max(), tol)
 
 
 def _check_selinv(book, feature, S, A, Lf, fv, case, Ax, beta):
@@ -183,7 +266,7 @@ def real_case(book, case, with_budget=True):
         Ad = R.dense_symmetric(n, Ap, Ai, Ax, beta)
         Lref = np.linalg.cholesky(_permuted(Ad, fv))
         if first:
-            _check_factor(book, "factor", fv, Lref)
+            _check_factor(book, "factor", fv, Lref, by_supernode=case["kind"] == "arrow")
             # 2. the solves (solve_device_cases.TOL per column; P and Pt bit for bit)
             P = np.asarray(fv.Perm)
             xs = None
@@ -264,6 +347,13 @@ def real_case(book, case, with_budget=True):
         err, dead = _grad_compare(Go, ref, mask)
         book.check("outer_grad", f"Gx against the dense formula, nrhs {nrhs}", err, R.tolerance(R.factor_rcond(fv)))
         book.check("outer_grad", "dead triangles of Gx, bits", dead, 0)
+        # 7b. the Schur complements and the condensed solves, for the m of device_fuzz_corpus.schur_ms: after both backward
+        # sweeps have used the plan, before the factor is replaced.  Their random inputs come from a generator of their own.
+        rng7 = DC.schur_rng(case)
+        ms = DC.case_ms(case, fv, rng7)
+        Mp = _permuted(Ad, fv)
+        sc = _check_schur(book, S, Lf, fv, Mp, ms, n)
+        _check_condensed(book, S, Lf, fv, Ad, Mp, sc, ms, case["nrhs"], rng7)
         # 8. new values from the device and another beta: the old values scaled per row and column, as
         # selinv_cases.case_stale does; both sweeps' results are stale, then those of the new matrix
         scale = 1.0 + 0.5 * rng.uniform(size=n)
@@ -281,6 +371,14 @@ def real_case(book, case, with_budget=True):
                 _check_selinv(book, "factorize_device", S, A, Lf, fv, case, Ax2, case["beta2"])
             else:
                 _check_factor_grad(book, "factorize_device", S, A, Lf, fv, Lref2, 2000 + case["case"])
+                # ... and one Schur complement again: that of the new matrix, not the one formed before
+                m = ms[0]
+                new = S.schur_device(Lf, m).cpu().numpy()
+                _guard(S)
+                ref = SR.dense_schur(_permuted(R.dense_symmetric(n, Ap, Ai, Ax2, case["beta2"]), fv), m)
+                book.check("schur", f"Sc m {m} of the new values", np.abs(new - ref).max() / np.abs(ref).max(),
+                           R.tolerance(R.factor_rcond(fv)))
+                book.check("schur", f"Sc m {m} of the new values is the old one", int(np.array_equal(new, sc[m][0])), 0)
         _done(S, A, Lf)
         return Zx, Gx, si_launches, fg_launches, chunks
     finally:
@@ -308,6 +406,7 @@ def complex_case(book, case):
     for the triangular systems, TOL_RES for the residual of A x = b, P / Pt / D bit for bit), the residual at 1e-11
     relative to |B|, one refinement step"""
     n, Ap, Ai, Ax, beta = case["n"], case["Ap"], case["Ai"], case["Ax"], case["beta"]
+    feat = "complex_arrow" if case["leaves"] else "complex_solve"
     if case["twin"]:
         os.environ["CHOLMOD_HIP_CX_TWIN"] = "1"
     else:
@@ -317,17 +416,21 @@ def complex_case(book, case):
         S, A, Lf, ok = DC.factorized(case, use_gpu=1)
         _guard(S)
         if not ok or Lf.contents.xtype != ch.COMPLEX:
-            book.check("complex_solve", f"factorize: status {S.cm.status} minor {int(Lf.contents.minor)}", 1, 0)
+            book.check(feat, f"factorize: status {S.cm.status} minor {int(Lf.contents.minor)}", 1, 0)
             _done(S, A, Lf)
             return
         twin = C.cast(Lf.contents.cx_twin, C.POINTER(ch.Factor)).contents.hip_is_twin
-        book.check("complex_solve", f"the storage asked for (hip_is_twin {twin})", int(twin != (1 if case["twin"] else 2)), 0)
+        book.check(feat, f"the storage asked for (hip_is_twin {twin})", int(twin != (1 if case["twin"] else 2)), 0)
         fv = _host_factor(S, Lf)
         Md = CX.full_hermitian(n, Ap, Ai, Ax).toarray() + beta * np.eye(n)
         P = np.asarray(fv.Perm)
         Mp = Md[np.ix_(P, P)]
         Lref = np.linalg.cholesky(Mp)
-        book.check("complex_solve", "L", np.linalg.norm(CX.dense_L(fv, fv.x) - Lref) / np.linalg.norm(Lref), TOL_L)
+        book.check(feat, "L", np.linalg.norm(CX.dense_L(fv, fv.x) - Lref) / np.linalg.norm(Lref), TOL_L)
+        if case["leaves"]:
+            dead, imag = _check_by_supernode(book, feat, fv, Lref)
+            book.check(feat, "dead triangles of L", dead, 0)
+            book.check(feat, "imaginary parts of the diagonal of L", imag, 0)
         for nrhs in case["nrhs"]:
             b = CX._rhs(rng, nrhs, n)
             B = _dev(b)
@@ -337,20 +440,20 @@ def complex_case(book, case):
             ipb[:, P] = b
             for name, sys_, ref in (("L", ch.SYS_L, lower), ("LD", ch.SYS_LD, lower), ("Lt", ch.SYS_Lt, upper), ("DLt", ch.SYS_DLt, upper)):
                 x = S.solve_device(Lf, B, sys_).cpu().numpy()
-                book.check("complex_solve", f"{name} nrhs {nrhs}", CX._relcols(x, ref), CX.TOL)
+                book.check(feat, f"{name} nrhs {nrhs}", CX._relcols(x, ref), CX.TOL)
             for name, sys_, Mx in (("A", ch.SYS_A, Md), ("LDLt", ch.SYS_LDLt, Mp)):       # (LDLt: L L' x = b, no permutation)
                 x = S.solve_device(Lf, B, sys_).cpu().numpy()
                 r = (Mx @ x.T).T - b
-                book.check("complex_solve", f"{name} nrhs {nrhs}, residual",
+                book.check(feat, f"{name} nrhs {nrhs}, residual",
                            max(np.linalg.norm(r[k]) / np.linalg.norm(b[k]) for k in range(nrhs)), CX.TOL_RES)
             for name, sys_, ref in (("P", ch.SYS_P, b[:, P]), ("Pt", ch.SYS_Pt, ipb), ("D", ch.SYS_D, b)):
                 x = S.solve_device(Lf, B, sys_).cpu().numpy()
-                book.check("complex_solve", f"{name} nrhs {nrhs}, entries that differ", np.count_nonzero(x != ref), 0)
+                book.check(feat, f"{name} nrhs {nrhs}, entries that differ", np.count_nonzero(x != ref), 0)
             _guard(S)
             x0 = CX._rhs(rng, nrhs, n)
             r = S.residual_device(Lf, _dev(x0), B).cpu().numpy()
             ref = b - (Md @ x0.T).T
-            book.check("complex_solve", f"residual nrhs {nrhs}",
+            book.check(feat, f"residual nrhs {nrhs}",
                        max(np.linalg.norm(r[k] - ref[k]) / np.linalg.norm(b[k]) for k in range(nrhs)), 1e-11)
         xs = S.solve_device(Lf, B).cpu().numpy()
         xp = xs * (1.0 + 1e-6 * CX._rhs(rng, len(b), n))
@@ -359,7 +462,7 @@ def complex_case(book, case):
         x1 = X.cpu().numpy()
         _guard(S)
         after = max(np.linalg.norm(b[k] - Md @ x1[k]) / np.linalg.norm(b[k]) for k in range(len(b)))
-        book.check("complex_solve", "one refinement step", after, TOL_REFINE)
+        book.check(feat, "one refinement step", after, TOL_REFINE)
         _done(S, A, Lf)
     finally:
         os.environ.pop("CHOLMOD_HIP_CX_TWIN", None)
@@ -402,6 +505,10 @@ def aat_case(book, case):
     g = S.aat_logdet_grad_device(A, Lf, _dev(a)).cpu().numpy()
     _guard(S)
     book.check("aat", "aat_logdet_grad_device", np.abs(g - ref["grad_values"] / 0.3).max(), AR.bars(M, a, ref, tol, 1)[0] / 0.3)
+    # the Schur complement of the A A' + beta I factor, for the edge draw of device_fuzz_corpus.schur_ms (the factor is the
+    # one the calls above left: of the same values and beta)
+    fv = _host_factor(S, Lf)
+    _check_schur(book, S, Lf, fv, _permuted((M @ M.T).toarray() + beta * np.eye(m), fv), DC.case_ms(case, fv)[:1], m)
     _done(S, A, Lf)
 
 

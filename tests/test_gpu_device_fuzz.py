@@ -1,15 +1,17 @@
 """The device-resident features on a seeded random corpus (tests/device_fuzz_corpus.py: Poisson, banded and general random
 SPD patterns under natural, nested-dissection and random orderings, block arrows with engineered front shapes, complex
-Hermitian and unsymmetric A A' cases; n <= 700), every result against a dense float64 reference at the bar the project
+Hermitian and unsymmetric A A' cases, complex Hermitian block arrows on the edges of the complex kernels; n <= 700), the
+Schur complement and the condensed solves among them, every result against a dense float64 reference at the bar the project
 already holds that feature to.  tests/test_device_fuzz_corpus.py shows on the CPU that the corpus reaches every dispatch
-class of the two backward sweeps and of the device solves, that the bar stays at 1e-12 and that the references alone use
+class of the two backward sweeps and of the device solves, every path of the Schur tile kernel's walk and every twin-space
+front class of the complex kernels, that the bar stays at 1e-12 and that the references alone use
 less than a tenth of it.
 
 One child process per seed (tests/device_fuzz_runner.py: torch has to be imported before the engine library is loaded)
-runs all 40 cases; its result is cached, and every feature has its own verdict: the child exited 0, the feature ran at
+runs all 46 cases; its result is cached, and every feature has its own verdict: the child exited 0, the feature ran at
 least one check, none failed.  The worst err / tol of the feature is printed.
 
-Wall time of one child on an MI355X, measured: 10 s for seed 3 and 11 s for seed 11 (40 cases each), most of it the dense
+Wall time of one child on an MI355X, measured: 14 s for seed 3 and 13 s for seed 11 (46 cases each), most of it the dense
 references on the host."""
 import json
 import os
@@ -23,9 +25,9 @@ pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SEEDS = [3, 11]             # device_fuzz_corpus.SEEDS, NCASE (kept literal here so that collection needs no scipy work)
-NCASE = 40
+NCASE = 46
 FEATURES = ["factor", "solve", "residual_refine", "selinv", "logdet", "values_grad", "factor_grad", "outer_grad",
-            "factorize_device", "budget_bits", "complex_solve", "aat"]
+            "factorize_device", "budget_bits", "complex_solve", "aat", "schur", "schur_condensed", "complex_arrow"]
 
 _runs = {}
 

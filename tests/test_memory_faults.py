@@ -6,6 +6,7 @@ CHOLMOD_OUT_OF_MEMORY, and a factorization that fails on a symbolic L must hand 
 (CHOLMOD/Supernodal/cholmod_super_numeric.c:235-248).  CPU path here; the GPU path in tests/test_gpu_edge_and_demo.py."""
 import ctypes as C
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +16,14 @@ from suitesparse_amd import generators as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FA_PATH = os.path.join(ROOT, "tests", "faultalloc", "libfaultalloc.so")
+
+
+def fault_library():
+    """tests/faultalloc's library.  __graft_entry__.build () makes it; where the file is gone since (a tests directory put
+    back from its sources after the build) it is made again from the committed source, by the same make call."""
+    if not os.path.exists(FA_PATH):
+        subprocess.check_call(["make", "-C", os.path.dirname(FA_PATH), "-s"])
+    return C.CDLL(FA_PATH)
 
 
 class SSConfig(C.Structure):
@@ -28,7 +37,7 @@ class FaultAllocator:
 
     def __init__(self, lib):
         self.lib = lib
-        self.fa = C.CDLL(FA_PATH)
+        self.fa = fault_library()
         self.fa.fa_arm.argtypes = [C.c_long]
         self.fa.fa_calls.restype = C.c_long
         self.fa.fa_failed.restype = C.c_long
