@@ -444,8 +444,7 @@ int cholmod_hip_selinv_info (cholmod_hip_plan *plan, double *out8) ;
  * the sum over the trailing supernodes of (rows from the first trailing column down)^2 x (trailing columns) multiply-adds,
  * at most about m^3 / 3.
  * Ordered on `stream` exactly as the selected inverse is: the engine stream waits for an event recorded on it, `stream`
- * waits for the engine's completion event; the first call creates the two events, after that nothing is allocated and the
- * host does not wait.  No host-device copy.  Not during capture.
+ * waits for the engine's completion event; nothing is allocated and the host does not wait.  No host-device copy.  Not during capture.
  * CHOLMOD_HIP_INVALID, before any device call, for a NULL plan, a host-only plan, several ranks, the plan of a complex factor,
  * no positive definite numeric factor on the device, m < 0 or m > n, a leading dimension < m, both outputs NULL. */
 int cholmod_hip_schur_device (cholmod_hip_plan *plan, int64_t m, double *dS, int64_t lds, double *dF, int64_t ldf,
@@ -519,7 +518,7 @@ int cholmod_hip_factor_grad_info (cholmod_hip_plan *plan, double *out8) ;
  * lanes reads a row as one 128-byte line; with fewer they are read in place, right-hand sides in index order.  The two
  * paths may differ by rounding.
  * Ordered on `stream` exactly as cholmod_hip_solve_device is (not during capture).  The first call of either path
- * allocates its workspace (events; two panels [n][16]); after that nothing is allocated and the host does not wait.
+ * allocates its workspace (two panels [n][16]); after that nothing is allocated and the host does not wait.
  * Work is divided by entries of S; the column of an entry comes from an i32 column-of-entry array (4 bytes of HBM per
  * entry of S) that the first call after a cholmod_hip_upload_matrix builds on the device, without a host wait.
  * Needs a resident packed S with its value map, not a numeric factor.  CHOLMOD_HIP_INVALID, before any device call: a NULL

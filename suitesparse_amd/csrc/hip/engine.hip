@@ -27,8 +27,6 @@ static void free_device (cholmod_hip_plan *P)
     drop_product_map (P) ;
     selinv_free (P) ;
     grad_free (P) ;
-    for (hipEvent_t e : {P->fv_ev_in, P->fv_ev_out}) if (e) (void) hipEventDestroy (e) ;
-    P->fv_ev_in = P->fv_ev_out = nullptr ;
     if (P->prog_dev) { (void) hipHostFree (P->prog_dev) ; P->prog_dev = nullptr ; }
     if (P->h_vals) { (void) hipHostFree (P->h_vals) ; P->h_vals = nullptr ; }
     for (auto e : P->chunk_ev) (void) hipEventDestroy (e) ;
@@ -47,7 +45,7 @@ static void free_device (cholmod_hip_plan *P)
     if (P->stream2) (void) hipStreamDestroy (P->stream2) ;
     if (P->ev0) (void) hipEventDestroy (P->ev0) ;
     if (P->ev1) (void) hipEventDestroy (P->ev1) ;
-    for (hipEvent_t e : {P->sd_ev_in, P->sd_ev0, P->sd_ev1, P->rs_ev_out, P->sc_ev_in, P->sc_ev_out}) if (e) (void) hipEventDestroy (e) ;
+    for (hipEvent_t e : {P->user_ev_in, P->user_ev_out, P->sd_ev0, P->sd_ev1}) if (e) (void) hipEventDestroy (e) ;
     if (P->stream) (void) hipStreamDestroy (P->stream) ;
 }
 
@@ -58,6 +56,8 @@ static int upload_plan (cholmod_hip_plan *P)
     auto pnow = [] () { return std::chrono::duration<double> (std::chrono::steady_clock::now ().time_since_epoch ()).count () ; } ;
     double tu0 = pnow () ;
     HIPCHK (hipStreamCreate (&P->stream)) ;
+    HIPCHK (hipEventCreateWithFlags (&P->user_ev_in, hipEventDisableTiming)) ;
+    HIPCHK (hipEventCreateWithFlags (&P->user_ev_out, hipEventDisableTiming)) ;
     if (const char *e = TEST_ENV ("CHOLMOD_HIP_TEST_JITTER"))
     {
         unsigned long long seed = 0 ; int mx = 2000 ;
@@ -1166,9 +1166,9 @@ int cholmod_hip_set_product_map (cholmod_hip_plan *P, const int64_t *cp, const i
     if (e == hipSuccess) P->d_pm_order = dupload (order, e) ;
     if (e != hipSuccess)
     {
-        (void) hipGetLastError () ;
+        const int rc = alloc_failure (e) ;
         drop_product_map (P) ;
-        return e == hipErrorOutOfMemory ? CHOLMOD_HIP_OUT_OF_MEMORY : CHOLMOD_HIP_GPU_PROBLEM ;
+        return rc ;
     }
     for (int k = 0 ; k < 4 ; k++) P->pm_class [k] = first [k] ;
     P->pm_na = navalues ;
@@ -1183,16 +1183,12 @@ int cholmod_hip_set_product_map (cholmod_hip_plan *P, const int64_t *cp, const i
 int cholmod_hip_factorize_values_device (cholmod_hip_plan *P, const double *dvalues, int64_t nvalues,
     double beta, int quick_return_if_not_posdef, void *stream, int64_t *minor)
 {
-    if (!P || P->host_only || !dvalues || !minor || P->world > 1) return CHOLMOD_HIP_INVALID ;
-    if (P->flags & (CHOLMOD_HIP_CX_STORAGE | CHOLMOD_HIP_PHI_TWIN)) return CHOLMOD_HIP_INVALID ;       // real factors only
+    if (!real_device_plan (P) || !dvalues || !minor) return CHOLMOD_HIP_INVALID ;
     if (!P->d_Sp || !P->d_vsrc || P->s_unpacked || P->vsrc_nz != P->s_cur_nz) return CHOLMOD_HIP_INVALID ;
     if (nvalues != (P->pm_set ? P->pm_na : P->vals_n)) return CHOLMOD_HIP_INVALID ;
     if (P->values_begun) return CHOLMOD_HIP_INVALID ;           // (a host upload is under way: its factorization comes first)
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    if (!P->fv_ev_in) HIPCHK (hipEventCreateWithFlags (&P->fv_ev_in, hipEventDisableTiming)) ;
-    if (!P->fv_ev_out) HIPCHK (hipEventCreateWithFlags (&P->fv_ev_out, hipEventDisableTiming)) ;
-    HIPCHK (hipEventRecord (P->fv_ev_in, user)) ;
-    HIPCHK (hipStreamWaitEvent (st, P->fv_ev_in, 0)) ;
+    HIP_TRY (stream_enter (P, user)) ;
     const double *vals = dvalues ;
     if (P->pm_set)
     {
@@ -1212,9 +1208,9 @@ int cholmod_hip_factorize_values_device (cholmod_hip_plan *P, const double *dval
     const int rc = run_factorize (P, beta, quick_return_if_not_posdef, &m) ;
     *minor = m ;
     if (rc < 0) return rc ;
-    // (run_factorize has waited for the engine stream: what the caller enqueues next finds the factor, and dvalues is free)
-    HIPCHK (hipEventRecord (P->fv_ev_out, st)) ;
-    HIPCHK (hipStreamWaitEvent (user, P->fv_ev_out, 0)) ;
+    // (run_factorize has checked the launches and waited for the engine stream: what the caller enqueues next finds the
+    // factor, and dvalues is free)
+    HIP_TRY (stream_rejoin (P, user)) ;
     return rc ;
 }
 
@@ -1282,7 +1278,7 @@ int cholmod_hip_factor_checks (cholmod_hip_plan *P, double *out5)
     if (!P || P->host_only || !out5) return CHOLMOD_HIP_INVALID ;
     for (int q = 0 ; q < 5 ; q++) out5 [q] = 0 ;
     if (P->nsuper == 0) return CHOLMOD_HIP_OK ;
-    { int rc = ensure_check_tasks (P) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
+    HIP_TRY (ensure_check_tasks (P)) ;
     HIPCHK (hipMemsetAsync (P->d_chk_out, 0, 5 * sizeof (double), P->stream)) ;
     // (several ranks: the complete factor exists only after cholmod_hip_gather_factor)
     if (!whole_factor (P) || !whole_fronts (P)) return CHOLMOD_HIP_INVALID ;
@@ -1304,7 +1300,7 @@ int cholmod_hip_diag_minmax (cholmod_hip_plan *P, double *out3)
     out3 [0] = out3 [1] = out3 [2] = 0 ;
     if (P->n == 0) return CHOLMOD_HIP_OK ;
     if (!whole_factor (P) || !whole_fronts (P)) return CHOLMOD_HIP_INVALID ;
-    { int rc = ensure_check_tasks (P) ; if (rc != CHOLMOD_HIP_OK) return rc ; }     // (d_chk_out: five doubles of scratch)
+    HIP_TRY (ensure_check_tasks (P)) ;     // (d_chk_out: five doubles of scratch)
     unsigned long long seed [3] ;
     const double inf = INFINITY, zero = 0.0 ;
     memcpy (&seed [0], &inf, 8) ; memcpy (&seed [1], &zero, 8) ; seed [2] = 0 ;
@@ -1373,7 +1369,7 @@ int cholmod_hip_download_even_columns (cholmod_hip_plan *P, double *out_host)
         HIPCHK (hipMemcpy (out_host, whole_factor (P), (size_t) P->xsize * sizeof (double), hipMemcpyDeviceToHost)) ;
         return CHOLMOD_HIP_OK ;
     }
-    { int rc = ensure_check_tasks (P) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
+    HIP_TRY (ensure_check_tasks (P)) ;
     double *tmp = nullptr ;
     const size_t bytes = (size_t) (P->xsize / 2) * sizeof (double) ;
     if (hipMalloc ((void **) &tmp, bytes) != hipSuccess) { (void) hipGetLastError () ; return CHOLMOD_HIP_OUT_OF_MEMORY ; }

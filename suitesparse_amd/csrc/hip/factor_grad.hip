@@ -13,23 +13,19 @@
 
 namespace {
 
-#define FG_TRY(call) do { int rc_ = (call) ; if (rc_ != CHOLMOD_HIP_OK) return rc_ ; } while (0)
-
 // Gx, the scratch and the program (sweep_ensure), the partial sums of the trace, the attributes of the kernels; nothing is
 // allocated once they exist
 static int ensure (cholmod_hip_plan *P)
 {
-    FG_TRY (sweep_ensure (P, &SelInv::d_Gx)) ;
+    HIP_TRY (sweep_ensure (P, &SelInv::d_Gx)) ;
     SelInv *S = P->si ;
     if (!S->d_tr)
     {
-        const hipError_t e = hipMalloc ((void **) &S->d_tr, (size_t) std::max<i64> ((P->n + 255) / 256, 1) * sizeof (double)) ;
-        if (e != hipSuccess)
+        const int rc = device_alloc (&S->d_tr, (P->n + 255) / 256) ;
+        if (rc != CHOLMOD_HIP_OK)
         {
-            (void) hipGetLastError () ;
-            S->d_tr = nullptr ;
             sweep_release (P, &SelInv::d_Gx) ;          // (the factor is untouched)
-            return e == hipErrorOutOfMemory ? CHOLMOD_HIP_OUT_OF_MEMORY : CHOLMOD_HIP_GPU_PROBLEM ;
+            return rc ;
         }
     }
     if (!S->fg_ready)
@@ -76,16 +72,16 @@ static void run (cholmod_hip_plan *P, hipStream_t st)
 // One sweep behind the caller's stream: `seed` enqueues what leaves Lbar in Gx (a launch that the clock and info [1] count)
 template <typename F> static int sweep (cholmod_hip_plan *P, void *stream, F seed)
 {
-    FG_TRY (ensure (P)) ;
+    HIP_TRY (ensure (P)) ;
     SelInv *S = P->si ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
     P->fg_valid = false ;
-    FG_TRY (sweep_enter (P, user)) ;
+    HIP_TRY (stream_enter (P, user)) ;
     HIPCHK (hipEventRecord (S->fg_clock.ev0, st)) ;
-    if (P->xsize > 0) FG_TRY (seed (S->d_Gx, st)) ;
+    if (P->xsize > 0) HIP_TRY (seed (S->d_Gx, st)) ;
     run (P, st) ;
     HIPCHK (hipEventRecord (S->fg_clock.ev1, st)) ;
-    FG_TRY (sweep_leave (P, user)) ;
+    HIP_TRY (stream_leave (P, user)) ;
     S->fg_clock.launches = (long) S->steps.size () + 1 ;
     S->fg_clock.pending = true ;
     P->fg_valid = true ;
@@ -134,7 +130,7 @@ int cholmod_hip_factor_grad_gather_device (cholmod_hip_plan *P, double *dG, int6
     const i64 n = P->n, nparts = (n + 255) / 256 ;
     SelInv *S = P->si ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    FG_TRY (sweep_enter (P, user)) ;
+    HIP_TRY (stream_enter (P, user)) ;
     if (dG && nvalues > 0)
     {
         // every value the factorization does not read: +0.0, in a pass of its own ahead of the writes through src []
@@ -150,7 +146,7 @@ int cholmod_hip_factor_grad_gather_device (cholmod_hip_plan *P, double *dG, int6
                 (const double *) S->d_Gx, S->d_tr) ;
         hipLaunchKernelGGL (k_fg_trace_final, dim3 (1), dim3 (256), 0, st, nparts, (const double *) S->d_tr, dTrace) ;
     }
-    return sweep_leave (P, user) ;
+    return stream_leave (P, user) ;
 }
 
 int cholmod_hip_factor_grad_download (cholmod_hip_plan *P, double *Gx_host)

@@ -14,29 +14,11 @@ struct Grad {
     double *d_U = nullptr, *d_V = nullptr ;     // the panels [n][16] of U and V in the factor's ordering
     double *d_part = nullptr ;                  // partial sums of the log-determinant, one per 256 columns
     i32 *d_col = nullptr ; i64 col_cap = 0 ;    // the column of every entry of the resident S (P->gr_index_valid)
-    hipEvent_t ev_in = nullptr, ev_out = nullptr ;
 } ;
 
 namespace {
 
-#define GR_TRY(call) do { int rc_ = (call) ; if (rc_ != CHOLMOD_HIP_OK) return rc_ ; } while (0)
-
-// what both entry points refuse, before any device call
-static bool bad_plan (const cholmod_hip_plan *P)
-{
-    if (!P || P->host_only || P->world > 1) return true ;
-    return (P->flags & (CHOLMOD_HIP_CX_STORAGE | CHOLMOD_HIP_PHI_TWIN)) != 0 ;          // real factors only
-}
-
-static int alloc (double **into, i64 count)
-{
-    if (*into) return CHOLMOD_HIP_OK ;
-    const hipError_t e = hipMalloc ((void **) into, (size_t) std::max<i64> (count, 1) * sizeof (double)) ;
-    if (e == hipSuccess) return CHOLMOD_HIP_OK ;
-    (void) hipGetLastError () ;
-    *into = nullptr ;
-    return e == hipErrorOutOfMemory ? CHOLMOD_HIP_OUT_OF_MEMORY : CHOLMOD_HIP_GPU_PROBLEM ;
-}
+static int alloc (double **into, i64 count) { return *into ? CHOLMOD_HIP_OK : device_alloc (into, count) ; }
 
 // The column-of-entry array of the resident S, next to the residual's transposed index: void when S is uploaded anew,
 // built by the first call after that -- on the engine stream, from Sp alone, without a host wait; its buffer is kept
@@ -49,13 +31,7 @@ static int ensure_index (cholmod_hip_plan *P)
     if (nz > g->col_cap || !g->d_col)
     {
         if (g->d_col) { HIPCHK (hipStreamSynchronize (P->stream)) ; (void) hipFree (g->d_col) ; g->d_col = nullptr ; g->col_cap = 0 ; }
-        const hipError_t e = hipMalloc ((void **) &g->d_col, (size_t) std::max<i64> (nz, 1) * sizeof (i32)) ;
-        if (e != hipSuccess)
-        {
-            (void) hipGetLastError () ;
-            g->d_col = nullptr ;
-            return e == hipErrorOutOfMemory ? CHOLMOD_HIP_OUT_OF_MEMORY : CHOLMOD_HIP_GPU_PROBLEM ;
-        }
+        HIP_TRY (device_alloc (&g->d_col, nz)) ;
         g->col_cap = std::max<i64> (nz, 1) ;
     }
     if (nz > 0)
@@ -64,37 +40,18 @@ static int ensure_index (cholmod_hip_plan *P)
     return CHOLMOD_HIP_OK ;
 }
 
-// the events; `panels`: the two panels; `partials`: the buffer of the log-determinant.  Nothing is allocated once they exist.
+// `panels`: the two panels; `partials`: the buffer of the log-determinant.  Nothing is allocated once they exist.
 static int ensure (cholmod_hip_plan *P, bool panels, bool partials)
 {
     if (!P->gr) P->gr = new (std::nothrow) Grad ;
     Grad *g = P->gr ;
     if (!g) return CHOLMOD_HIP_OUT_OF_MEMORY ;
-    if (!g->ev_in) HIPCHK (hipEventCreateWithFlags (&g->ev_in, hipEventDisableTiming)) ;
-    if (!g->ev_out) HIPCHK (hipEventCreateWithFlags (&g->ev_out, hipEventDisableTiming)) ;
     if (panels)
     {
-        GR_TRY (alloc (&g->d_U, P->n * GR_NP)) ;
-        GR_TRY (alloc (&g->d_V, P->n * GR_NP)) ;
+        HIP_TRY (alloc (&g->d_U, P->n * GR_NP)) ;
+        HIP_TRY (alloc (&g->d_V, P->n * GR_NP)) ;
     }
-    if (partials) GR_TRY (alloc (&g->d_part, (P->n + 255) / 256)) ;
-    return CHOLMOD_HIP_OK ;
-}
-
-// the engine stream takes its place in the caller's order: behind what the caller has enqueued ...
-static int enter (cholmod_hip_plan *P, hipStream_t user)
-{
-    HIPCHK (hipEventRecord (P->gr->ev_in, user)) ;
-    HIPCHK (hipStreamWaitEvent (P->stream, P->gr->ev_in, 0)) ;
-    return CHOLMOD_HIP_OK ;
-}
-
-// ... and ahead of what the caller enqueues next
-static int leave (cholmod_hip_plan *P, hipStream_t user)
-{
-    HIPCHK (hipGetLastError ()) ;
-    HIPCHK (hipEventRecord (P->gr->ev_out, P->stream)) ;
-    HIPCHK (hipStreamWaitEvent (user, P->gr->ev_out, 0)) ;
+    if (partials) HIP_TRY (alloc (&g->d_part, (P->n + 255) / 256)) ;
     return CHOLMOD_HIP_OK ;
 }
 
@@ -132,7 +89,7 @@ static void sampled_product (cholmod_hip_plan *P, int perm, double alpha, const 
 
 // ---- through a product map ---------------------------------------------------------------------------------------------------
 
-// what the two product entry points ask of the plan beyond bad_plan: the value map of the current resident packed S, and a
+// what the two product entry points ask of the plan beyond real_device_plan: the value map of the current resident packed S, and a
 // product map from navalues values onto it
 static bool bad_product_plan (const cholmod_hip_plan *P, i64 navalues)
 {
@@ -144,9 +101,7 @@ template <typename T> static int upload (T **into, const std::vector<T> &v)
 {
     hipError_t e = hipMalloc ((void **) into, std::max<size_t> (v.size (), 1) * sizeof (T)) ;
     if (e == hipSuccess && !v.empty ()) e = hipMemcpy (*into, v.data (), v.size () * sizeof (T), hipMemcpyHostToDevice) ;
-    if (e == hipSuccess) return CHOLMOD_HIP_OK ;
-    (void) hipGetLastError () ;
-    return e == hipErrorOutOfMemory ? CHOLMOD_HIP_OUT_OF_MEMORY : CHOLMOD_HIP_GPU_PROBLEM ;
+    return e == hipSuccess ? CHOLMOD_HIP_OK : alloc_failure (e) ;
 }
 
 // The transposed product map and the scratch of vals_n doubles, built by the first gradient call after a
@@ -230,7 +185,6 @@ void grad_free (cholmod_hip_plan *P)
     if (!g) return ;
     P->gr_index_valid = false ;
     for (void *d : {(void *) g->d_U, (void *) g->d_V, (void *) g->d_part, (void *) g->d_col}) if (d) (void) hipFree (d) ;
-    for (hipEvent_t e : {g->ev_in, g->ev_out}) if (e) (void) hipEventDestroy (e) ;
     delete g ;
 }
 
@@ -239,74 +193,74 @@ extern "C" {
 int cholmod_hip_values_grad_device (cholmod_hip_plan *P, int perm, double alpha, const double *dU, int64_t ldu,
     const double *dV, int64_t ldv, int64_t nrhs, double *dG, int64_t nvalues, void *stream)
 {
-    if (bad_plan (P) || !dU || !dV || !dG || nrhs < 0 || ldu < P->n || ldv < P->n) return CHOLMOD_HIP_INVALID ;
+    if (!real_device_plan (P) || !dU || !dV || !dG || nrhs < 0 || ldu < P->n || ldv < P->n) return CHOLMOD_HIP_INVALID ;
     // the value map of the current resident packed S, and values that are given, not computed
     if (!P->d_Sp || !P->d_vsrc || P->s_unpacked || P->vsrc_nz != P->s_cur_nz || nvalues != P->vals_n || P->pm_set)
         return CHOLMOD_HIP_INVALID ;
     if (perm && !P->d_perm) return CHOLMOD_HIP_INVALID ;                                // cholmod_hip_set_perm first
     if (P->n == 0 || nvalues == 0) return CHOLMOD_HIP_OK ;
-    GR_TRY (ensure (P, nrhs >= SD_BLOCK_MIN_NRHS, false)) ;
-    GR_TRY (ensure_index (P)) ;
+    HIP_TRY (ensure (P, nrhs >= SD_BLOCK_MIN_NRHS, false)) ;
+    HIP_TRY (ensure_index (P)) ;
     hipStream_t user = (hipStream_t) stream ;
-    GR_TRY (enter (P, user)) ;
+    HIP_TRY (stream_enter (P, user)) ;
     sampled_product (P, perm, alpha, dU, (i64) ldu, dV, (i64) ldv, (i64) nrhs, dG, (i64) nvalues) ;
-    return leave (P, user) ;
+    return stream_leave (P, user) ;
 }
 
 int cholmod_hip_logdet_device (cholmod_hip_plan *P, double *dOut, void *stream)
 {
-    if (bad_plan (P) || !dOut) return CHOLMOD_HIP_INVALID ;
+    if (!real_device_plan (P) || !dOut) return CHOLMOD_HIP_INVALID ;
     if (P->factor_state != 1 || !P->d_Lx) return CHOLMOD_HIP_INVALID ;  // no numeric factor on the device, or one that is not positive definite
-    GR_TRY (ensure (P, false, true)) ;
+    HIP_TRY (ensure (P, false, true)) ;
     const i64 n = P->n, nparts = (n + 255) / 256 ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    GR_TRY (enter (P, user)) ;
+    HIP_TRY (stream_enter (P, user)) ;
     if (nparts > 0)
         hipLaunchKernelGGL (k_gr_logdet_partial, dim3 ((unsigned) nparts), dim3 (256), 0, st, n, P->d_supermap, P->d_fr, P->d_Lx, P->gr->d_part) ;
     hipLaunchKernelGGL (k_gr_logdet_final, dim3 (1), dim3 (256), 0, st, nparts, (const double *) P->gr->d_part, dOut) ;
-    return leave (P, user) ;
+    return stream_leave (P, user) ;
 }
 
 int cholmod_hip_product_values_grad_device (cholmod_hip_plan *P, int perm, double alpha, const double *dU, int64_t ldu,
     const double *dV, int64_t ldv, int64_t nrhs, const double *dA, double *dGa, int64_t navalues, void *stream)
 {
-    if (bad_plan (P) || !dU || !dV || !dA || !dGa || nrhs < 0 || ldu < P->n || ldv < P->n) return CHOLMOD_HIP_INVALID ;
+    if (!real_device_plan (P) || !dU || !dV || !dA || !dGa || nrhs < 0 || ldu < P->n || ldv < P->n) return CHOLMOD_HIP_INVALID ;
     if (bad_product_plan (P, navalues)) return CHOLMOD_HIP_INVALID ;
     if (perm && !P->d_perm) return CHOLMOD_HIP_INVALID ;                                // cholmod_hip_set_perm first
     if (P->n == 0 || navalues == 0) return CHOLMOD_HIP_OK ;
     hipStream_t user = (hipStream_t) stream ;
     if (nrhs == 0 || P->vals_n == 0)                    // nothing to sample: the gradient is +0.0 whatever dA holds
     {
-        GR_TRY (ensure (P, false, false)) ;
-        GR_TRY (enter (P, user)) ;
+        HIP_TRY (ensure (P, false, false)) ;
+        HIP_TRY (stream_enter (P, user)) ;
         hipLaunchKernelGGL (k_gr_zero_fill, dim3 (blocks_of (navalues)), dim3 (256), 0, P->stream, (i64) navalues, dGa) ;
-        return leave (P, user) ;
+        return stream_leave (P, user) ;
     }
-    GR_TRY (ensure (P, nrhs >= SD_BLOCK_MIN_NRHS, false)) ;
-    GR_TRY (ensure_index (P)) ;
-    GR_TRY (ensure_transposed (P)) ;
-    GR_TRY (enter (P, user)) ;
+    HIP_TRY (ensure (P, nrhs >= SD_BLOCK_MIN_NRHS, false)) ;
+    HIP_TRY (ensure_index (P)) ;
+    HIP_TRY (ensure_transposed (P)) ;
+    HIP_TRY (stream_enter (P, user)) ;
     sampled_product (P, perm, alpha, dU, (i64) ldu, dV, (i64) ldv, (i64) nrhs, P->d_pt_gvals, P->vals_n) ;
     product_grad (P, dA, dGa) ;
-    return leave (P, user) ;
+    return stream_leave (P, user) ;
 }
 
 int cholmod_hip_product_logdet_grad_device (cholmod_hip_plan *P, const double *dA, double *dGa, int64_t navalues, void *stream)
 {
-    if (bad_plan (P) || !dA || !dGa || bad_product_plan (P, navalues)) return CHOLMOD_HIP_INVALID ;
+    if (!real_device_plan (P) || !dA || !dGa || bad_product_plan (P, navalues)) return CHOLMOD_HIP_INVALID ;
     // a current selected inverse of a positive definite factor (cholmod_hip_selinv_device first)
     if (P->factor_state != 1 || !P->si_valid || !P->si) return CHOLMOD_HIP_INVALID ;
     if (P->n == 0 || navalues == 0) return CHOLMOD_HIP_OK ;
     hipStream_t user = (hipStream_t) stream ;
-    GR_TRY (ensure (P, false, false)) ;
-    GR_TRY (ensure_index (P)) ;
-    GR_TRY (ensure_transposed (P)) ;
-    GR_TRY (enter (P, user)) ;
+    HIP_TRY (ensure (P, false, false)) ;
+    HIP_TRY (ensure_index (P)) ;
+    HIP_TRY (ensure_transposed (P)) ;
+    HIP_TRY (stream_enter (P, user)) ;
     // Z at the values S reads, once on the diagonal and twice off it; +0.0, never the gather's NaN, at every other value
     hipLaunchKernelGGL (k_gr_zero_fill, dim3 (blocks_of (std::max<i64> (P->vals_n, 1))), dim3 (256), 0, P->stream, P->vals_n, P->d_pt_gvals) ;
     selinv_gather_logdet_grad (P, P->gr->d_col, P->d_pt_gvals, P->stream) ;
     product_grad (P, dA, dGa) ;
-    return leave (P, user) ;
+    return stream_leave (P, user) ;
 }
 
 } // extern "C"

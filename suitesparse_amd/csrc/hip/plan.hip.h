@@ -105,6 +105,8 @@ struct Launch {
 #define HIPCHK(call) do { hipError_t e_ = (call) ; if (e_ != hipSuccess) { \
     fprintf (stderr, "cholmod_hip: %s failed: %s (%s:%d)\n", #call, \
         hipGetErrorString (e_), __FILE__, __LINE__) ; return CHOLMOD_HIP_GPU_PROBLEM ; } } while (0)
+// a step that returns a status: the first failure is the caller's result
+#define HIP_TRY(call) do { int rc_ = (call) ; if (rc_ != CHOLMOD_HIP_OK) return rc_ ; } while (0)
 // (solves, checks) K<true> for a complex factor in its own storage; needs `cxs` in scope
 #define CXS_LAUNCH(K, ...) do { if (cxs) hipLaunchKernelGGL (K<true>, __VA_ARGS__) ; else hipLaunchKernelGGL (K<false>, __VA_ARGS__) ; } while (0)
 
@@ -308,6 +310,9 @@ struct cholmod_hip_plan {
     // device
     hipStream_t stream = nullptr ;          // main stream
     hipStream_t stream2 = nullptr ;         // exchange stream (exchange look-ahead of a shared front's next block column)
+    // every entry point that works on a caller's stream (stream_enter, stream_leave below): the event the engine stream
+    // waits for on the caller's stream and the one the caller's stream waits for; created with the stream, no timing
+    hipEvent_t user_ev_in = nullptr, user_ev_out = nullptr ;
     std::vector<hipEvent_t> sync_ev ;       // schedule events (no timing)
     i64 *d_Ls = nullptr ;
     FrontD *d_fr = nullptr ;
@@ -353,11 +358,9 @@ struct cholmod_hip_plan {
     int *d_first_fail = nullptr ;           // k_first_fail result
     i64 *d_vsrc = nullptr ; double *d_vals = nullptr ;      // value map of the resident S (cholmod_hip_set_value_map)
     i64 vsrc_nz = 0, vals_n = 0, s_cur_nz = 0 ;
-    // values from device memory (cholmod_hip_factorize_values_device): the event the engine stream waits for on the
-    // caller's stream and the one the caller's stream waits for; and the product map (cholmod_hip_set_product_map): the
-    // vals_n values of the value map are sums of products of the pm_na values the caller passes -- lists (pm_cp, pm_ia,
-    // pm_ib), the entries sorted by list length into the three classes of k_product_values (pm_order, pm_class [0 .. 3])
-    hipEvent_t fv_ev_in = nullptr, fv_ev_out = nullptr ;
+    // the product map (cholmod_hip_set_product_map): the vals_n values of the value map are sums of products of the pm_na
+    // values the caller of cholmod_hip_factorize_values_device passes -- lists (pm_cp, pm_ia, pm_ib), the entries sorted by
+    // list length into the three classes of k_product_values (pm_order, pm_class [0 .. 3])
     i64 *d_pm_cp = nullptr, *d_pm_ia = nullptr, *d_pm_ib = nullptr ; i32 *d_pm_order = nullptr ;
     i64 pm_class [4] = {0, 0, 0, 0}, pm_na = 0 ;
     bool pm_set = false ;
@@ -390,29 +393,25 @@ struct cholmod_hip_plan {
     double *d_X = nullptr ; i64 x_cap = 0 ;
     i64 *d_perm = nullptr ;                 // the fill-reducing permutation (cholmod_hip_set_perm)
     // device-resident solve (cholmod_hip_solve_device): the panel workspace W [n][16], the accumulators of the 16-wide
-    // backward walk ([sb_max_tasks][256][16], zero between solves), the event the engine stream waits for on the
-    // caller's stream and the two that time the solve (read by cholmod_hip_get_stats)
+    // backward walk ([sb_max_tasks][256][16], zero between solves), the two events that time the solve (read by
+    // cholmod_hip_get_stats; the caller's stream waits for the second)
     double *d_sd_W = nullptr, *d_sd_acc = nullptr ;
-    hipEvent_t sd_ev_in = nullptr, sd_ev0 = nullptr, sd_ev1 = nullptr ;
+    hipEvent_t sd_ev0 = nullptr, sd_ev1 = nullptr ;
     bool sd_time_pending = false ;
     // device-resident residual and refinement (residual.hip): the transposed index of the resident S -- per row its
     // entries left of the diagonal, column and position in d_Sx (built at the first call, void when S is uploaded anew)
-    // --, two more panels [n][16] for X and B in the factor's ordering, the event the caller's stream waits for
+    // --, two more panels [n][16] for X and B in the factor's ordering
     i64 *d_rs_Tp = nullptr, *d_rs_Tq = nullptr ; i32 *d_rs_Tj = nullptr ; bool rs_index_valid = false ;
     double *d_rs_X = nullptr, *d_rs_B = nullptr ;
-    hipEvent_t rs_ev_out = nullptr ;
-    // selected inverse (selinv.hip): its program, buffers and events live behind `si`.  factor_state follows the numeric
+    // selected inverse (selinv.hip): its program, buffers and clocks live behind `si`.  factor_state follows the numeric
     // factor in d_Lx (0: none, 1: positive definite, 2: the last factorization was not); si_valid: Zx belongs to that factor
     // The factor gradient (factor_grad.hip) runs the same program on the same scratch with kernels of its own; its array Gx
     // lives behind `si` as well, fg_valid: Gx belongs to that factor.
     struct SelInv *si = nullptr ;
     bool si_valid = false, fg_valid = false ;
     int factor_state = 0 ;
-    // Schur complement and trailing multiplies (schur.hip): the event the engine stream waits for on the caller's stream
-    // and the one the caller's stream waits for (created by the first call)
-    hipEvent_t sc_ev_in = nullptr, sc_ev_out = nullptr ;
-    // gradients and the log-determinant (grad.hip): two panels, the partial sums, the column of every entry of the
-    // resident S (built at the first call, void when S is uploaded anew) and the events live behind `gr`
+    // gradients and the log-determinant (grad.hip): two panels, the partial sums and the column of every entry of the
+    // resident S (built at the first call, void when S is uploaded anew) live behind `gr`
     struct Grad *gr = nullptr ;
     bool gr_index_valid = false ;
     // progress of the running factorization, readable from another host thread (cholmod_hip_progress): the host side
@@ -433,6 +432,56 @@ struct cholmod_hip_plan {
 // rank's own array when there is one rank, the gathered copy otherwise (nullptr before a gather).
 static inline double *whole_factor (cholmod_hip_plan *P) { return P->world == 1 ? P->d_Lx : (P->full_valid ? P->d_Lx_full : nullptr) ; }
 static inline const FrontD *whole_fronts (cholmod_hip_plan *P) { return P->world == 1 ? P->d_fr : P->d_fr_full ; }
+
+// ---- what the entry points that work on a caller's stream and on the device-resident factor share ----------------------------
+
+// a real, single-rank plan on a device: what the features that serve real factors only ask first
+static inline bool real_device_plan (const cholmod_hip_plan *P)
+{
+    if (!P || P->host_only || P->world > 1) return false ;
+    return (P->flags & (CHOLMOD_HIP_CX_STORAGE | CHOLMOD_HIP_PHI_TWIN)) == 0 ;
+}
+
+// The engine stream takes its place in the caller's order: behind what the caller has enqueued ...  (One pair of events
+// serves every entry point: all of them enqueue on the one in-order engine stream, from a host that calls one at a time,
+// and a wait binds to the record that precedes it, so an event may be recorded again while an earlier wait is outstanding.)
+static inline int stream_enter (cholmod_hip_plan *P, hipStream_t user)
+{
+    HIPCHK (hipEventRecord (P->user_ev_in, user)) ;
+    HIPCHK (hipStreamWaitEvent (P->stream, P->user_ev_in, 0)) ;
+    return CHOLMOD_HIP_OK ;
+}
+
+// ... and ahead of what the caller enqueues next
+static inline int stream_rejoin (cholmod_hip_plan *P, hipStream_t user)
+{
+    HIPCHK (hipEventRecord (P->user_ev_out, P->stream)) ;
+    HIPCHK (hipStreamWaitEvent (user, P->user_ev_out, 0)) ;
+    return CHOLMOD_HIP_OK ;
+}
+
+// ... once the launches since stream_enter are known to have been accepted
+static inline int stream_leave (cholmod_hip_plan *P, hipStream_t user)
+{
+    HIPCHK (hipGetLastError ()) ;
+    return stream_rejoin (P, user) ;
+}
+
+// a failed allocation: the error is cleared, and out of memory is told from a problem of the GPU
+static inline int alloc_failure (hipError_t e)
+{
+    (void) hipGetLastError () ;
+    return e == hipErrorOutOfMemory ? CHOLMOD_HIP_OUT_OF_MEMORY : CHOLMOD_HIP_GPU_PROBLEM ;
+}
+
+// `count` (at least one) elements of device memory into *into, which stays nullptr on failure
+template <typename T> static int device_alloc (T **into, i64 count)
+{
+    const hipError_t e = hipMalloc ((void **) into, (size_t) std::max<i64> (count, 1) * sizeof (T)) ;
+    if (e == hipSuccess) return CHOLMOD_HIP_OK ;
+    *into = nullptr ;
+    return alloc_failure (e) ;
+}
 
 // selinv.hip: everything the selected inverse holds of a plan (cholmod_hip_plan_destroy)
 void selinv_free (cholmod_hip_plan *P) ;

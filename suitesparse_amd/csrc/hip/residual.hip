@@ -65,11 +65,10 @@ static bool bad_plan (const cholmod_hip_plan *P, int perm)
 // workspaces and index; nothing is allocated once they exist
 static int rs_ensure (cholmod_hip_plan *P, bool with_factor, bool columns)
 {
-    { int rc = sd_ensure (P, with_factor, columns) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
+    HIP_TRY (sd_ensure (P, with_factor, columns)) ;
     const size_t panel = (size_t) P->n * SD_NP * sizeof (double) ;
     if (!P->d_rs_X) HIPCHK (hipMalloc ((void **) &P->d_rs_X, panel)) ;
     if (!P->d_rs_B) HIPCHK (hipMalloc ((void **) &P->d_rs_B, panel)) ;
-    if (!P->rs_ev_out) HIPCHK (hipEventCreateWithFlags (&P->rs_ev_out, hipEventDisableTiming)) ;
     return P->rs_index_valid ? CHOLMOD_HIP_OK : build_index (P) ;
 }
 
@@ -121,25 +120,13 @@ struct Group {
     }
 } ;
 
-// the engine stream takes its place in the caller's order: behind what the caller has enqueued ...
+// behind what the caller has enqueued (stream_enter), the norms begin at zero
 static int enter (cholmod_hip_plan *P, hipStream_t user, double *dRnorm, i64 nrhs)
 {
-    HIPCHK (hipEventRecord (P->sd_ev_in, user)) ;
-    HIPCHK (hipStreamWaitEvent (P->stream, P->sd_ev_in, 0)) ;
+    HIP_TRY (stream_enter (P, user)) ;
     if (dRnorm) HIPCHK (hipMemsetAsync (dRnorm, 0, nrhs * sizeof (double), P->stream)) ;
     return CHOLMOD_HIP_OK ;
 }
-
-// ... and ahead of what the caller enqueues next
-static int leave (cholmod_hip_plan *P, hipStream_t user)
-{
-    HIPCHK (hipGetLastError ()) ;
-    HIPCHK (hipEventRecord (P->rs_ev_out, P->stream)) ;
-    HIPCHK (hipStreamWaitEvent (user, P->rs_ev_out, 0)) ;
-    return CHOLMOD_HIP_OK ;
-}
-
-#define RS_TRY(call) do { int rc_ = (call) ; if (rc_ != CHOLMOD_HIP_OK) return rc_ ; } while (0)
 
 } // namespace
 
@@ -151,22 +138,22 @@ int cholmod_hip_residual_device (cholmod_hip_plan *P, int perm, const double *dX
     const i64 n = P->n ;
     if (nrhs == 0 || n == 0) return CHOLMOD_HIP_OK ;
     const bool columns = nrhs < SD_BLOCK_MIN_NRHS ;
-    RS_TRY (rs_ensure (P, false, columns)) ;
+    HIP_TRY (rs_ensure (P, false, columns)) ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    RS_TRY (enter (P, user, dRnorm, nrhs)) ;
+    HIP_TRY (enter (P, user, dRnorm, nrhs)) ;
     const i64 *pm = perm ? P->d_perm : nullptr ;
     double *W = P->d_sd_W, *Xp = P->d_rs_X ;
     const i64 step = columns ? nrhs : SD_NP ;
     for (i64 r0 = 0 ; r0 < nrhs ; r0 += step)
     {
         const Group g {P, st, columns, (int) std::min<i64> (step, nrhs - r0)} ;
-        RS_TRY (g.load (pm, dX + r0 * ldx, ldx, Xp)) ;
-        RS_TRY (g.load (pm, dB + r0 * ldb, ldb, W)) ;
+        HIP_TRY (g.load (pm, dX + r0 * ldx, ldx, Xp)) ;
+        HIP_TRY (g.load (pm, dB + r0 * ldb, ldb, W)) ;
         g.residual (Xp, W, W) ;
         g.norms (W, dRnorm ? dRnorm + r0 : nullptr) ;
-        RS_TRY (g.store (pm, W, dR + r0 * ldr, ldr)) ;
+        HIP_TRY (g.store (pm, W, dR + r0 * ldr, ldr)) ;
     }
-    return leave (P, user) ;
+    return stream_leave (P, user) ;
 }
 
 int cholmod_hip_refine_device (cholmod_hip_plan *P, int perm, const double *dB, int64_t ldb, double *dX, int64_t ldx,
@@ -179,9 +166,9 @@ int cholmod_hip_refine_device (cholmod_hip_plan *P, int perm, const double *dB, 
     const FrontD *frw = whole_fronts (P) ;
     if (steps > 0 && (!Lw || !frw)) return CHOLMOD_HIP_INVALID ;
     const bool columns = nrhs < SD_BLOCK_MIN_NRHS ;
-    RS_TRY (rs_ensure (P, steps > 0, columns)) ;
+    HIP_TRY (rs_ensure (P, steps > 0, columns)) ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    RS_TRY (enter (P, user, dRnorm, nrhs)) ;
+    HIP_TRY (enter (P, user, dRnorm, nrhs)) ;
     if (steps > 0) refresh_inverses (P, frw, Lw, (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0) ;
     const i64 *pm = perm ? P->d_perm : nullptr ;
     double *W = P->d_sd_W, *Xp = P->d_rs_X, *Bp = P->d_rs_B ;
@@ -190,8 +177,8 @@ int cholmod_hip_refine_device (cholmod_hip_plan *P, int perm, const double *dB, 
     {
         // the whole iteration in the factor's ordering: B and X pass through Perm once each way
         const Group g {P, st, columns, (int) std::min<i64> (step, nrhs - r0)} ;
-        RS_TRY (g.load (pm, dB + r0 * ldb, ldb, Bp)) ;
-        RS_TRY (g.load (pm, dX + r0 * ldx, ldx, Xp)) ;
+        HIP_TRY (g.load (pm, dB + r0 * ldb, ldb, Bp)) ;
+        HIP_TRY (g.load (pm, dX + r0 * ldx, ldx, Xp)) ;
         for (int s = 0 ; s < steps ; s++)
         {
             g.residual (Xp, Bp, W) ;
@@ -202,7 +189,7 @@ int cholmod_hip_refine_device (cholmod_hip_plan *P, int perm, const double *dB, 
             g.residual (Xp, Bp, W) ;
             g.norms (W, dRnorm + r0) ;
         }
-        if (steps > 0) RS_TRY (g.store (pm, Xp, dX + r0 * ldx, ldx)) ;
+        if (steps > 0) HIP_TRY (g.store (pm, Xp, dX + r0 * ldx, ldx)) ;
     }
-    return leave (P, user) ;
+    return stream_leave (P, user) ;
 }

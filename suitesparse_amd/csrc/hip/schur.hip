@@ -3,37 +3,10 @@
 // Cholesky factor of Sc), and the products L22 V and L22' V that turn the L and L' sweeps of solve.hip into the condensed
 // right-hand side and the back-expansion (cholmod_hip_trailing_multiply_device).  Kernels: schur_kernels.hip.h.  Nothing
 // here touches the factorization, its schedule or its workspaces: the kernels read Lx, the row lists, the front
-// descriptors and the supernode map, which are on the device already, and write the caller's arrays only.  The two events
-// that order the engine stream against the caller's are created by the first call; nothing is allocated after it.  No
-// test hook reaches this file: it is built once for both libraries.
+// descriptors and the supernode map, which are on the device already, and write the caller's arrays only: nothing is
+// allocated here.  No test hook reaches this file: it is built once for both libraries.
 #include "schur_kernels.hip.h"
 #include "selinv_internal.hip.h"
-
-namespace {
-
-// the engine stream takes its place in the caller's order: behind what the caller has enqueued ...
-static int schur_enter (cholmod_hip_plan *P, hipStream_t user)
-{
-    if (!P->sc_ev_in)
-    {
-        HIPCHK (hipEventCreateWithFlags (&P->sc_ev_in, hipEventDisableTiming)) ;
-        HIPCHK (hipEventCreateWithFlags (&P->sc_ev_out, hipEventDisableTiming)) ;
-    }
-    HIPCHK (hipEventRecord (P->sc_ev_in, user)) ;
-    HIPCHK (hipStreamWaitEvent (P->stream, P->sc_ev_in, 0)) ;
-    return CHOLMOD_HIP_OK ;
-}
-
-// ... and ahead of what the caller enqueues next
-static int schur_leave (cholmod_hip_plan *P, hipStream_t user)
-{
-    HIPCHK (hipGetLastError ()) ;
-    HIPCHK (hipEventRecord (P->sc_ev_out, P->stream)) ;
-    HIPCHK (hipStreamWaitEvent (user, P->sc_ev_out, 0)) ;
-    return CHOLMOD_HIP_OK ;
-}
-
-} // namespace
 
 extern "C" {
 
@@ -46,14 +19,14 @@ int cholmod_hip_schur_device (cholmod_hip_plan *P, int64_t m, double *dS, int64_
     const i64 nt = (m + 63) / 64, ntiles = nt * (nt + 1) / 2 ;
     if (ntiles > INT32_MAX) return CHOLMOD_HIP_INVALID ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    { int rc = schur_enter (P, user) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
+    HIP_TRY (stream_enter (P, user)) ;
     if (dS)
         hipLaunchKernelGGL (k_schur_tile, dim3 ((unsigned) ntiles), dim3 (256), 0, st, n, (i64) m, (int) nt,
             (int) P->supermap [n - m], (int) P->nsuper, P->d_fr, P->d_Ls, P->d_Lx, dS, (i64) lds) ;
     if (dF)
         hipLaunchKernelGGL (k_schur_factor, dim3 ((unsigned) m), dim3 (256), 0, st, n, (i64) m, P->d_supermap, P->d_fr, P->d_Ls,
             P->d_Lx, dF, (i64) ldf) ;
-    return schur_leave (P, user) ;
+    return stream_leave (P, user) ;
 }
 
 int cholmod_hip_trailing_multiply_device (cholmod_hip_plan *P, int64_t m, int trans, const double *dV, int64_t ldv, double *dOut,
@@ -64,7 +37,7 @@ int cholmod_hip_trailing_multiply_device (cholmod_hip_plan *P, int64_t m, int tr
     if (m == 0 || nrhs == 0) return CHOLMOD_HIP_OK ;
     const i64 n = P->n ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    { int rc = schur_enter (P, user) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
+    HIP_TRY (stream_enter (P, user)) ;
     if (trans)
         hipLaunchKernelGGL (k_schur_mult_t, dim3 ((unsigned) m), dim3 (256), 0, st, n, (i64) m, P->d_supermap, P->d_fr, P->d_Ls,
             P->d_Lx, dV, (i64) ldv, dOut, (i64) ldo, (i64) nrhs) ;
@@ -75,7 +48,7 @@ int cholmod_hip_trailing_multiply_device (cholmod_hip_plan *P, int64_t m, int tr
         hipLaunchKernelGGL (k_schur_mult_n, dim3 ((unsigned) m), dim3 (256), 0, st, n, (i64) m, P->d_supermap, P->d_fr, P->d_Ls,
             P->d_Lx, dV, (i64) ldv, dOut, (i64) ldo, (i64) nrhs) ;
     }
-    return schur_leave (P, user) ;
+    return stream_leave (P, user) ;
 }
 
 } // extern "C"

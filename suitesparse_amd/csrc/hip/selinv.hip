@@ -12,15 +12,13 @@
 // writer by construction, and a batch may be cut into chunks anywhere.  The scratch is the squares of one chunk plus
 // one 64 x 64 partial per 64-row slice of its fronts; thin fronts need none (LDS).  info [5] counts both buffers.
 //
-// The launch program built here (Builder), the scratch and the stream events are shared with the factor gradient
-// (factor_grad.hip, through selinv_internal.hip.h: sweep_ensure, sweep_release, sweep_enter, sweep_leave, sweep_info): it
+// The launch program built here (Builder) and the scratch are shared with the factor gradient
+// (factor_grad.hip, through selinv_internal.hip.h: sweep_ensure, sweep_release, sweep_info): it
 // runs the same steps with kernels of its own, on the engine stream like this sweep, so the scratch has one user at a time.
 #include "selinv_kernels.hip.h"
 #include "selinv_internal.hip.h"
 
 namespace {
-
-#define SI_TRY(call) do { int rc_ = (call) ; if (rc_ != CHOLMOD_HIP_OK) return rc_ ; } while (0)
 
 // doubles of scratch the chunks of a batch may take (the largest front always fits): CHOLMOD_HIP_SELINV_BUDGET_MB, 2 GiB
 static i64 scratch_budget ()
@@ -151,7 +149,7 @@ struct Builder {
     }
 } ;
 
-// once per plan: the program, its task lists on the device, the events
+// once per plan: the program, its task lists on the device, the clocks
 static int prepare (cholmod_hip_plan *P, SelInv *S)
 {
     Builder {P, *S}.build () ;
@@ -162,8 +160,6 @@ static int prepare (cholmod_hip_plan *P, SelInv *S)
     S->d_tasks = dupload (S->tasks, e) ; HIPCHK (e) ;
     S->d_slots = dupload (S->slots, e) ; HIPCHK (e) ;
     S->d_thin = dupload (S->thin, e) ; HIPCHK (e) ;
-    HIPCHK (hipEventCreateWithFlags (&S->ev_in, hipEventDisableTiming)) ;
-    HIPCHK (hipEventCreateWithFlags (&S->ev_out, hipEventDisableTiming)) ;
     for (SweepClock *c : {&S->si_clock, &S->fg_clock})
     {
         HIPCHK (hipEventCreate (&c->ev0)) ;
@@ -222,13 +218,11 @@ int sweep_ensure (cholmod_hip_plan *P, double *SelInv::*result)
     for (int k = 0 ; k < 3 ; k++)
     {
         if (*into [k]) continue ;
-        const hipError_t e = hipMalloc ((void **) into [k], (size_t) std::max<i64> (want [k], 1) * sizeof (double)) ;
-        mine [k] = (e == hipSuccess) ;
-        if (e == hipSuccess) continue ;
-        (void) hipGetLastError () ;
-        *into [k] = nullptr ;
+        const int rc = device_alloc (into [k], want [k]) ;
+        mine [k] = (rc == CHOLMOD_HIP_OK) ;
+        if (mine [k]) continue ;
         for (int q = 0 ; q < k ; q++) if (mine [q]) { (void) hipFree (*into [q]) ; *into [q] = nullptr ; }   // (the factor is untouched)
-        return e == hipErrorOutOfMemory ? CHOLMOD_HIP_OUT_OF_MEMORY : CHOLMOD_HIP_GPU_PROBLEM ;
+        return rc ;
     }
     return CHOLMOD_HIP_OK ;
 }
@@ -241,21 +235,6 @@ void sweep_release (cholmod_hip_plan *P, double *SelInv::*result)
     if (S->d_Zx || S->d_Gx) return ;
     for (void *d : {(void *) S->d_M, (void *) S->d_P}) if (d) (void) hipFree (d) ;
     S->d_M = S->d_P = nullptr ;
-}
-
-int sweep_enter (cholmod_hip_plan *P, hipStream_t user)
-{
-    HIPCHK (hipEventRecord (P->si->ev_in, user)) ;
-    HIPCHK (hipStreamWaitEvent (P->stream, P->si->ev_in, 0)) ;
-    return CHOLMOD_HIP_OK ;
-}
-
-int sweep_leave (cholmod_hip_plan *P, hipStream_t user)
-{
-    HIPCHK (hipGetLastError ()) ;
-    HIPCHK (hipEventRecord (P->si->ev_out, P->stream)) ;
-    HIPCHK (hipStreamWaitEvent (user, P->si->ev_out, 0)) ;
-    return CHOLMOD_HIP_OK ;
 }
 
 void sweep_info (SelInv *S, SweepClock &c, double *out8)
@@ -281,7 +260,7 @@ void selinv_free (cholmod_hip_plan *P)
     if (!S) return ;
     for (void *d : {(void *) S->d_Zx, (void *) S->d_Gx, (void *) S->d_tr, (void *) S->d_M, (void *) S->d_P, (void *) S->d_tasks,
         (void *) S->d_slots, (void *) S->d_thin}) if (d) (void) hipFree (d) ;
-    for (hipEvent_t e : {S->ev_in, S->ev_out, S->si_clock.ev0, S->si_clock.ev1, S->fg_clock.ev0, S->fg_clock.ev1})
+    for (hipEvent_t e : {S->si_clock.ev0, S->si_clock.ev1, S->fg_clock.ev0, S->fg_clock.ev1})
         if (e) (void) hipEventDestroy (e) ;
     delete S ;
 }
@@ -299,15 +278,15 @@ extern "C" {
 int cholmod_hip_selinv_device (cholmod_hip_plan *P, void *stream)
 {
     if (sweep_bad_plan (P)) return CHOLMOD_HIP_INVALID ;
-    SI_TRY (sweep_ensure (P, &SelInv::d_Zx)) ;
+    HIP_TRY (sweep_ensure (P, &SelInv::d_Zx)) ;
     SelInv *S = P->si ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
     P->si_valid = false ;
-    SI_TRY (sweep_enter (P, user)) ;
+    HIP_TRY (stream_enter (P, user)) ;
     HIPCHK (hipEventRecord (S->si_clock.ev0, st)) ;
     run (P, st) ;
     HIPCHK (hipEventRecord (S->si_clock.ev1, st)) ;
-    SI_TRY (sweep_leave (P, user)) ;
+    HIP_TRY (stream_leave (P, user)) ;
     S->si_clock.pending = true ;
     P->si_valid = true ;
     return CHOLMOD_HIP_OK ;
@@ -327,7 +306,7 @@ int cholmod_hip_selinv_gather_device (cholmod_hip_plan *P, double *dZvalues, int
     if ((!dZvalues && !dDiag) || P->n == 0) return CHOLMOD_HIP_OK ;
     const i64 n = P->n ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    SI_TRY (sweep_enter (P, user)) ;
+    HIP_TRY (stream_enter (P, user)) ;
     const unsigned ncol = (unsigned) ((n + 255) / 256) ;
     if (dZvalues)
     {
@@ -339,7 +318,7 @@ int cholmod_hip_selinv_gather_device (cholmod_hip_plan *P, double *dZvalues, int
     if (dDiag)
         hipLaunchKernelGGL (k_si_gather_diag, dim3 (ncol), dim3 (256), 0, st, n, perm ? P->d_perm : nullptr, P->d_supermap,
             P->d_fr, P->si->d_Zx, dDiag) ;
-    return sweep_leave (P, user) ;
+    return stream_leave (P, user) ;
 }
 
 int cholmod_hip_selinv_download (cholmod_hip_plan *P, double *Zx_host)

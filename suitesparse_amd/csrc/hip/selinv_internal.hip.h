@@ -1,8 +1,8 @@
 // selinv_internal.hip.h -- what the two sweeps that run the factorization backwards share (selinv.hip: the selected
 // inverse; factor_grad.hip: reverse-mode Cholesky): the launch program -- the plan's batches from the last to the first, cut
 // into chunks under CHOLMOD_HIP_SELINV_BUDGET_MB, with their slots, tasks and partial offsets --, the scratch squares and
-// partials, and the events that order the engine stream against the caller's.  Both sweeps run on the engine stream, so
-// the scratch is never live in two of them.  Zx and Gx are separate arrays with separate staleness (P->si_valid,
+// partials.  Both sweeps run on the engine stream, behind the caller's (stream_enter, stream_leave: plan.hip.h), so the
+// scratch is never live in two of them.  Zx and Gx are separate arrays with separate staleness (P->si_valid,
 // P->fg_valid).  The program is built by selinv.hip (sweep_ensure); the kernels differ, the steps do not.
 #pragma once
 #include "sweep_device.hip.h"
@@ -28,7 +28,6 @@ struct SelInv {
     bool built = false ;
     SiTask *d_tasks = nullptr ; SiSlot *d_slots = nullptr ; i32 *d_thin = nullptr ;
     double *d_Zx = nullptr, *d_M = nullptr, *d_P = nullptr ;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr ;
     SweepClock si_clock ;
     // factor_grad.hip: Gx, the partial sums of its trace (one per 256 columns), its clock; fg_ready: its kernels'
     // attributes are set
@@ -40,19 +39,14 @@ struct SelInv {
 // what every entry point of both sweeps refuses, before any device call
 static inline bool sweep_bad_plan (const cholmod_hip_plan *P)
 {
-    if (!P || P->host_only || P->world > 1) return true ;
-    if (P->flags & (CHOLMOD_HIP_CX_STORAGE | CHOLMOD_HIP_PHI_TWIN)) return true ;       // real factors only
+    if (!real_device_plan (P)) return true ;
     return P->factor_state != 1 || !P->d_Lx ;       // no numeric factor on the device, or one that is not positive definite
 }
 
-// selinv.hip: the program (once per plan), the events, the scratch and the sweep's own array (xsize doubles) behind
+// selinv.hip: the program (once per plan), the clocks, the scratch and the sweep's own array (xsize doubles) behind
 // `result`: &SelInv::d_Zx or &SelInv::d_Gx; nothing is allocated once they exist.  A failure frees what the call allocated.
 int sweep_ensure (cholmod_hip_plan *P, double *SelInv::*result) ;
 // frees the sweep's own array, and the scratch if the other sweep holds no array either (the program stays)
 void sweep_release (cholmod_hip_plan *P, double *SelInv::*result) ;
-// the engine stream takes its place in the caller's order: behind what the caller has enqueued ...
-int sweep_enter (cholmod_hip_plan *P, hipStream_t user) ;
-// ... and ahead of what the caller enqueues next
-int sweep_leave (cholmod_hip_plan *P, hipStream_t user) ;
 // seconds and launches of a clock into out8 [0], [1] (may wait for the run), the program's flops into [2], [3]
 void sweep_info (SelInv *S, SweepClock &c, double *out8) ;

@@ -152,13 +152,13 @@ static int solve_workspace (cholmod_hip_plan *P, i64 solved, i64 acc_nrhs, bool 
     if (solved > P->solved_cap)
     {
         P->solved_cap = solved ;
-        { int rc = regrow (&P->d_solved, solved, false) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
+        HIP_TRY (regrow (&P->d_solved, solved, false)) ;
     }
     const i64 acc = (i64) P->sb_max_tasks * SOLVE_SB * acc_nrhs ;
     if (acc > P->sv_acc_cap)
     {
         P->sv_acc_cap = acc ;
-        { int rc = regrow (&P->d_sv_acc, acc, true) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
+        HIP_TRY (regrow (&P->d_sv_acc, acc, true)) ;
     }
     if (panel_acc && !P->d_sd_acc)
         return regrow (&P->d_sd_acc, (i64) std::max (P->sb_max_tasks, 1) * SOLVE_SB * SD_NP, true) ;
@@ -198,7 +198,7 @@ int cholmod_hip_solve (cholmod_hip_plan *P, int which, double *X, int64_t nrhs, 
         P->x_cap = need ;
     }
     hipStream_t st = P->stream ;
-    { int rc = solve_workspace (P, need, nrhs, false) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
+    HIP_TRY (solve_workspace (P, need, nrhs, false)) ;
     refresh_inverses (P, frw, Lw, cxs) ;
     HIPCHK (hipMemcpyAsync (P->d_X, X, need * sizeof (double), hipMemcpyHostToDevice, st)) ;
     HIPCHK (hipEventRecord (P->ev0, st)) ;
@@ -244,9 +244,8 @@ namespace sship {
 int sd_ensure (cholmod_hip_plan *P, bool with_factor, bool columns)
 {
     const i64 n = P->n ;
-    if (!P->sd_ev_in)
+    if (!P->sd_ev0)
     {
-        HIPCHK (hipEventCreateWithFlags (&P->sd_ev_in, hipEventDisableTiming)) ;
         HIPCHK (hipEventCreate (&P->sd_ev0)) ;
         HIPCHK (hipEventCreate (&P->sd_ev1)) ;
     }
@@ -310,11 +309,9 @@ int cholmod_hip_solve_device (cholmod_hip_plan *P, int which, int perm_in, int p
     // kernels rebuild the odd twin columns as they read (n, ld and the permutation are the twin's either way)
     const bool cxs = (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;
     const bool columns = nrhs < SD_BLOCK_MIN_NRHS ;
-    { int rc = sd_ensure (P, which != 3, columns) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
+    HIP_TRY (sd_ensure (P, which != 3, columns)) ;
     hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    // the engine stream takes its place in the caller's order: behind what the caller has enqueued ...
-    HIPCHK (hipEventRecord (P->sd_ev_in, user)) ;
-    HIPCHK (hipStreamWaitEvent (st, P->sd_ev_in, 0)) ;
+    HIP_TRY (stream_enter (P, user)) ;
     if (which != 3) refresh_inverses (P, frw, Lw, cxs) ;
     HIPCHK (hipEventRecord (P->sd_ev0, st)) ;
     const i64 *pin = perm_in ? P->d_perm : nullptr, *pout = perm_out ? P->d_perm : nullptr ;
@@ -323,9 +320,9 @@ int cholmod_hip_solve_device (cholmod_hip_plan *P, int which, int perm_in, int p
     if (columns)
     {
         // directly on the permuted columns, W as [nrhs][n]
-        { int rc = sd_move_columns (st, n, nrhs, pin, 0, dB, ldb, W, n) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
+        HIP_TRY (sd_move_columns (st, n, nrhs, pin, 0, dB, ldb, W, n)) ;
         if (which != 3) solve_sweeps (P, which, ColumnKernels {P, frw, Lw, st, W, n, (int) nrhs, cxs}) ;
-        { int rc = sd_move_columns (st, n, nrhs, pout, 1, W, n, dX, ldx) ; if (rc != CHOLMOD_HIP_OK) return rc ; }
+        HIP_TRY (sd_move_columns (st, n, nrhs, pout, 1, W, n, dX, ldx)) ;
     }
     else for (i64 r0 = 0 ; r0 < nrhs ; r0 += SD_NP)
     {
@@ -336,7 +333,7 @@ int cholmod_hip_solve_device (cholmod_hip_plan *P, int which, int perm_in, int p
     }
     HIPCHK (hipGetLastError ()) ;
     HIPCHK (hipEventRecord (P->sd_ev1, st)) ;
-    // ... and ahead of what the caller enqueues next
+    // the way out of stream_enter on the timed event: ahead of what the caller enqueues next
     HIPCHK (hipStreamWaitEvent (user, P->sd_ev1, 0)) ;
     // stats [24]: the two events are read by cholmod_hip_get_stats (a cholmod_hip_solve in between overwrites the mark)
     P->solve_seconds = -1.0 ;

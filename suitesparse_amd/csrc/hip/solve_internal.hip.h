@@ -16,7 +16,7 @@
 
 namespace sship {
 
-// workspaces of a device-resident solve (events, W [n][16]; with_factor: those of the sweeps, for fewer than
+// workspaces of a device-resident solve (its two timed events, W [n][16]; with_factor: those of the sweeps, for fewer than
 // SD_BLOCK_MIN_NRHS right-hand sides if `columns`, for panels otherwise); nothing is allocated once they exist
 int sd_ensure (cholmod_hip_plan *P, bool with_factor, bool columns) ;
 // the explicit inverses of the diagonal blocks of the big supernodes, recomputed on the engine stream if the factor

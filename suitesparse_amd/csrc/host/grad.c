@@ -8,32 +8,10 @@
  * argument is checked before a device is touched. */
 #include "host_internal.h"
 
-static int gr_status (int rc, cholmod_common *Common, const char *what)
-{
-    switch (rc)
-    {
-        case CHOLMOD_HIP_OK: return TRUE ;
-        case CHOLMOD_HIP_OUT_OF_MEMORY: ERROR (CHOLMOD_OUT_OF_MEMORY, what) ; return FALSE ;
-        case CHOLMOD_HIP_INVALID: ERROR (CHOLMOD_INVALID, what) ; return FALSE ;
-        default: ERROR (CHOLMOD_GPU_PROBLEM, what) ; return FALSE ;
-    }
-}
-
-/* what both entry points ask of L; TRUE: L->hip_plan holds the matrix L was last factorized from on the device */
-static int gr_factor_ready (cholmod_factor *L, int posdef, cholmod_common *Common)
-{
-    if (L->xtype == CHOLMOD_COMPLEX || L->xtype == CHOLMOD_ZOMPLEX)
-    { ERROR (CHOLMOD_NOT_INSTALLED, "gradients of a complex factor are not supported") ; return FALSE ; }
-    if (L->xtype != CHOLMOD_REAL || !L->is_super)
-    { ERROR (CHOLMOD_INVALID, "L must be a numeric supernodal factor") ; return FALSE ; }
-    if (posdef && L->minor < L->n) { ERROR (CHOLMOD_INVALID, "L is not positive definite") ; return FALSE ; }
-    /* the operands live in device memory: no fallback, whatever Common->hip_cpu_fallback says */
-    if (ssamd_resolve_use_gpu (Common) != 1) { ERROR (CHOLMOD_INVALID, "device gradients need Common->useGPU") ; return FALSE ; }
-    if (Common->hip_world > 1) { ERROR (CHOLMOD_INVALID, "device gradients run on one rank only") ; return FALSE ; }
-    if (!L->hip_plan || !L->hip_on_device)
-    { ERROR (CHOLMOD_INVALID, "L was not factorized on the device") ; return FALSE ; }
-    return TRUE ;
-}
+static const ssamd_device_feature grad_feature = {
+    "gradients of a complex factor are not supported", "device gradients need Common->useGPU",
+    "device gradients run on one rank only",
+    "gradients of a complex matrix are not supported", "the gradient needs a symmetric A (stype != 0)" } ;
 
 int cholmod_l_hip_values_grad_device (cholmod_sparse *A, cholmod_factor *L, double alpha, const double *U_dev, size_t ldu,
     const double *V_dev, size_t ldv, size_t nrhs, double *G_dev, void *stream, cholmod_common *Common)
@@ -45,36 +23,13 @@ int cholmod_l_hip_values_grad_device (cholmod_sparse *A, cholmod_factor *L, doub
     RETURN_IF_NULL (V_dev, FALSE) ;
     RETURN_IF_NULL (G_dev, FALSE) ;
     RETURN_IF_NULL (A->p, FALSE) ;
-    if (A->xtype == CHOLMOD_COMPLEX || A->xtype == CHOLMOD_ZOMPLEX)
-    { ERROR (CHOLMOD_NOT_INSTALLED, "gradients of a complex matrix are not supported") ; return FALSE ; }
-    if (L->xtype == CHOLMOD_COMPLEX || L->xtype == CHOLMOD_ZOMPLEX)
-    { ERROR (CHOLMOD_NOT_INSTALLED, "gradients of a complex factor are not supported") ; return FALSE ; }
-    if (A->xtype != CHOLMOD_REAL && A->xtype != CHOLMOD_PATTERN) { ERROR (CHOLMOD_INVALID, "invalid xtype") ; return FALSE ; }
-    /* (A*A' and column subsets: the caller's entries are then not the entries of the factorized matrix) */
-    if (A->stype == 0) { ERROR (CHOLMOD_INVALID, "the gradient needs a symmetric A (stype != 0)") ; return FALSE ; }
-    if (!A->packed) { ERROR (CHOLMOD_INVALID, "A must be packed") ; return FALSE ; }
-    if (A->nrow != L->n || A->nrow != A->ncol) { ERROR (CHOLMOD_INVALID, "A and L dimensions do not match") ; return FALSE ; }
-    if (ldu < L->n || ldv < L->n) { ERROR (CHOLMOD_INVALID, "leading dimension smaller than n") ; return FALSE ; }
-    const size_t annz = (size_t) ((Int *) A->p) [A->ncol] ;
-    if (annz > 0 && !A->i) { ERROR (CHOLMOD_INVALID, "argument missing") ; return FALSE ; }
-    if (!gr_factor_ready (L, FALSE, Common)) return FALSE ;
-    if (!L->hip_apat_valid)
-    { ERROR (CHOLMOD_INVALID, "L holds no pattern record: cholmod_l_factorize from a host matrix of this pattern first") ; return FALSE ; }
-    /* the proof that the plan's value map fits A, as in cholmod_l_hip_selinv_device: a mismatch touches no device state */
-    uint64_t hash [2] ;
-    hash [0] = ssamd_pattern_hash (A, &hash [1]) ;
-    if (L->hip_apat_nnz != annz || L->hip_apat_hash != hash [0] || L->hip_apat_hash2 != hash [1])
-    { ERROR (CHOLMOD_INVALID, "A does not have the pattern L was last factorized from") ; return FALSE ; }
+    size_t annz = 0 ;
+    if (!ssamd_values_matrix_fits (A, TRUE, L, ldu < ldv ? ldu : ldv, FALSE, &grad_feature, &annz, Common)) return FALSE ;
     Common->status = CHOLMOD_OK ;
     if (L->n == 0 || annz == 0) return TRUE ;
     cholmod_hip_plan *plan = (cholmod_hip_plan *) L->hip_plan ;
-    if (!L->hip_perm_set)
-    {
-        int rc = cholmod_hip_set_perm (plan, (const int64_t *) L->Perm) ;
-        if (rc != CHOLMOD_HIP_OK) return gr_status (rc, Common, "the permutation could not be stored on the device") ;
-        L->hip_perm_set = TRUE ;
-    }
-    return gr_status (cholmod_hip_values_grad_device (plan, 1, alpha, U_dev, (int64_t) ldu, V_dev, (int64_t) ldv,
+    if (!ssamd_perm_ready (L, Common)) return FALSE ;
+    return ssamd_device_status (cholmod_hip_values_grad_device (plan, 1, alpha, U_dev, (int64_t) ldu, V_dev, (int64_t) ldv,
         (int64_t) nrhs, G_dev, (int64_t) annz, stream), Common, "the plan holds no value map for this matrix") ;
 }
 
@@ -83,9 +38,9 @@ int cholmod_l_hip_logdet_device (cholmod_factor *L, double *out_dev, void *strea
     RETURN_IF_NULL_COMMON (FALSE) ;
     RETURN_IF_NULL (L, FALSE) ;
     RETURN_IF_NULL (out_dev, FALSE) ;
-    if (!gr_factor_ready (L, TRUE, Common)) return FALSE ;
+    if (!ssamd_resident_factor_ready (L, &grad_feature, TRUE, Common)) return FALSE ;
     Common->status = CHOLMOD_OK ;
-    return gr_status (cholmod_hip_logdet_device ((cholmod_hip_plan *) L->hip_plan, out_dev, stream), Common,
+    return ssamd_device_status (cholmod_hip_logdet_device ((cholmod_hip_plan *) L->hip_plan, out_dev, stream), Common,
         "the plan holds no positive definite factor on the device") ;
 }
 
@@ -96,10 +51,8 @@ int cholmod_l_hip_logdet_device (cholmod_factor *L, double *out_dev, void *strea
  * tril (A*A') with its product map. */
 static int gr_aat_ready (cholmod_sparse *A, cholmod_factor *L, int posdef, size_t ld, size_t *annz_out, cholmod_common *Common)
 {
-    if (A->xtype == CHOLMOD_COMPLEX || A->xtype == CHOLMOD_ZOMPLEX)
-    { ERROR (CHOLMOD_NOT_INSTALLED, "gradients of a complex matrix are not supported") ; return FALSE ; }
-    if (L->xtype == CHOLMOD_COMPLEX || L->xtype == CHOLMOD_ZOMPLEX)
-    { ERROR (CHOLMOD_NOT_INSTALLED, "gradients of a complex factor are not supported") ; return FALSE ; }
+    if (A->xtype == CHOLMOD_COMPLEX || A->xtype == CHOLMOD_ZOMPLEX) { ERROR (CHOLMOD_NOT_INSTALLED, grad_feature.complex_matrix) ; return FALSE ; }
+    if (L->xtype == CHOLMOD_COMPLEX || L->xtype == CHOLMOD_ZOMPLEX) { ERROR (CHOLMOD_NOT_INSTALLED, grad_feature.complex_factor) ; return FALSE ; }
     if (A->xtype != CHOLMOD_REAL && A->xtype != CHOLMOD_PATTERN) { ERROR (CHOLMOD_INVALID, "invalid xtype") ; return FALSE ; }
     if (A->stype != 0)
     { ERROR (CHOLMOD_INVALID, "the gradient through A*A' needs an unsymmetric A (stype == 0); a symmetric A: cholmod_l_hip_values_grad_device") ; return FALSE ; }
@@ -108,7 +61,7 @@ static int gr_aat_ready (cholmod_sparse *A, cholmod_factor *L, int posdef, size_
     if (ld < L->n) { ERROR (CHOLMOD_INVALID, "leading dimension smaller than n") ; return FALSE ; }
     const size_t annz = (size_t) ((Int *) A->p) [A->ncol] ;
     if (annz > 0 && !A->i) { ERROR (CHOLMOD_INVALID, "argument missing") ; return FALSE ; }
-    if (!gr_factor_ready (L, posdef, Common)) return FALSE ;
+    if (!ssamd_resident_factor_ready (L, &grad_feature, posdef, Common)) return FALSE ;
     if (!L->hip_apat_valid)
     { ERROR (CHOLMOD_INVALID, "L holds no pattern record: cholmod_l_factorize from a host matrix of this pattern first") ; return FALSE ; }
     Common->status = CHOLMOD_OK ;
@@ -134,13 +87,8 @@ int cholmod_l_hip_aat_values_grad_device (cholmod_sparse *A, cholmod_factor *L, 
     if (!gr_aat_ready (A, L, FALSE, ldu < ldv ? ldu : ldv, &annz, Common)) return FALSE ;
     if (L->n == 0 || annz == 0) return TRUE ;
     cholmod_hip_plan *plan = (cholmod_hip_plan *) L->hip_plan ;
-    if (!L->hip_perm_set)
-    {
-        int rc = cholmod_hip_set_perm (plan, (const int64_t *) L->Perm) ;
-        if (rc != CHOLMOD_HIP_OK) return gr_status (rc, Common, "the permutation could not be stored on the device") ;
-        L->hip_perm_set = TRUE ;
-    }
-    return gr_status (cholmod_hip_product_values_grad_device (plan, 1, alpha, U_dev, (int64_t) ldu, V_dev, (int64_t) ldv,
+    if (!ssamd_perm_ready (L, Common)) return FALSE ;
+    return ssamd_device_status (cholmod_hip_product_values_grad_device (plan, 1, alpha, U_dev, (int64_t) ldu, V_dev, (int64_t) ldv,
         (int64_t) nrhs, Avalues_dev, G_dev, (int64_t) annz, stream), Common, "the plan holds no product map for this matrix") ;
 }
 
@@ -157,11 +105,7 @@ int cholmod_l_hip_aat_logdet_grad_device (cholmod_sparse *A, cholmod_factor *L, 
     if (!gr_aat_ready (A, L, TRUE, L->n, &annz, Common)) return FALSE ;
     if (L->n == 0 || annz == 0) return TRUE ;
     cholmod_hip_plan *plan = (cholmod_hip_plan *) L->hip_plan ;
-    /* Zx of the plan current: computed now, on `stream`, if it is stale (as cholmod_l_hip_selinv_device does) */
-    double info [8] ;
-    int rc = cholmod_hip_selinv_info (plan, info) ;
-    if (rc == CHOLMOD_HIP_OK && info [6] == 0) rc = cholmod_hip_selinv_device (plan, stream) ;
-    if (rc != CHOLMOD_HIP_OK) return gr_status (rc, Common, "the selected inverse could not be computed on the device") ;
-    return gr_status (cholmod_hip_product_logdet_grad_device (plan, Avalues_dev, G_dev, (int64_t) annz, stream), Common,
+    if (!ssamd_selinv_current (plan, stream, Common)) return FALSE ;
+    return ssamd_device_status (cholmod_hip_product_logdet_grad_device (plan, Avalues_dev, G_dev, (int64_t) annz, stream), Common,
         "the plan holds no product map for this matrix") ;
 }

@@ -61,6 +61,20 @@ void ssamd_plan_ahead (cholmod_factor *L, cholmod_common *Common, const int64_t 
 int64_t ssamd_front_reach (const cholmod_sparse *U, const cholmod_factor *L, int64_t *reach_p, int32_t *reach_first) ;
 void ssamd_front_reach_alloc (const cholmod_sparse *U, const cholmod_factor *L, int64_t **reach_p, int32_t **reach_first) ;
 
+/* device_gate.c: what the entry points on the device-resident factor check alike.  The texts of one feature, verbatim
+ * (the last two: features that take a matrix A of values) */
+typedef struct
+{
+    const char *complex_factor, *use_gpu, *one_rank ;       /* L is complex; Common->useGPU is off; several ranks */
+    const char *complex_matrix, *unsymmetric_matrix ;       /* A is complex; A->stype is 0 */
+} ssamd_device_feature ;
+int ssamd_device_status (int rc, cholmod_common *Common, const char *what) ;
+int ssamd_resident_factor_ready (cholmod_factor *L, const ssamd_device_feature *feature, int need_posdef, cholmod_common *Common) ;
+int ssamd_values_matrix_fits (cholmod_sparse *A, int wanted, cholmod_factor *L, size_t ld, int need_posdef,
+    const ssamd_device_feature *feature, size_t *annz, cholmod_common *Common) ;
+int ssamd_perm_ready (cholmod_factor *L, cholmod_common *Common) ;
+int ssamd_selinv_current (cholmod_hip_plan *plan, void *stream, cholmod_common *Common) ;
+
 /* complex.c: complex / zomplex input through the real embedding */
 int ssamd_complex_super_numeric (cholmod_sparse *A, double beta, cholmod_factor *L, cholmod_common *Common) ;
 int ssamd_complex_sync_host (cholmod_factor *L, cholmod_common *Common) ;

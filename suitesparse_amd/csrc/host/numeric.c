@@ -1049,12 +1049,7 @@ int cholmod_l_hip_solve_device (int sys, cholmod_factor *L, const double *B_dev,
     const int which = (sys == CHOLMOD_A || sys == CHOLMOD_LDLt) ? 0
                     : (sys == CHOLMOD_L || sys == CHOLMOD_LD) ? 1
                     : (sys == CHOLMOD_Lt || sys == CHOLMOD_DLt) ? 2 : 3 ;
-    if ((perm_in || perm_out) && !L->hip_perm_set)
-    {
-        int rc = cholmod_hip_set_perm (plan, (const int64_t *) L->Perm) ;
-        if (rc != CHOLMOD_HIP_OK) return map_hip_status (rc, Common, "the permutation could not be stored on the device") ;
-        L->hip_perm_set = TRUE ;
-    }
+    if ((perm_in || perm_out) && !ssamd_perm_ready (L, Common)) return FALSE ;
     int rc = cholmod_hip_solve_device (plan, which, perm_in, perm_out, B_dev, (int64_t) ldb, X_dev, (int64_t) ldx,
         (int64_t) nrhs, stream) ;
     return (rc == CHOLMOD_HIP_OK) ? TRUE : map_hip_status (rc, Common, "HIP device solve failed") ;
@@ -1077,12 +1072,7 @@ static int residual_ready (cholmod_factor *L, size_t ld1, size_t ld2, size_t ld3
     { ERROR (CHOLMOD_INVALID, "no resident matrix: L was not factorized on the device") ; return FALSE ; }
     Common->status = CHOLMOD_OK ;
     if (nrhs == 0 || L->n == 0) return TRUE ;
-    if (!L->hip_perm_set)
-    {
-        int rc = cholmod_hip_set_perm ((cholmod_hip_plan *) L->hip_plan, (const int64_t *) L->Perm) ;
-        if (rc != CHOLMOD_HIP_OK) return map_hip_status (rc, Common, "the permutation could not be stored on the device") ;
-        L->hip_perm_set = TRUE ;
-    }
+    if (!ssamd_perm_ready (L, Common)) return FALSE ;
     *plan = (cholmod_hip_plan *) L->hip_plan ;
     return TRUE ;
 }

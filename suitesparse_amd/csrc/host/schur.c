@@ -6,42 +6,16 @@
  * argument is checked before a device is touched. */
 #include "host_internal.h"
 
-static int sc_status (int rc, cholmod_common *Common, const char *what)
-{
-    switch (rc)
-    {
-        case CHOLMOD_HIP_OK: return TRUE ;
-        case CHOLMOD_HIP_OUT_OF_MEMORY: ERROR (CHOLMOD_OUT_OF_MEMORY, what) ; return FALSE ;
-        case CHOLMOD_HIP_INVALID: ERROR (CHOLMOD_INVALID, what) ; return FALSE ;
-        default: ERROR (CHOLMOD_GPU_PROBLEM, what) ; return FALSE ;
-    }
-}
+static const ssamd_device_feature schur_feature = {
+    "the Schur complement of a complex factor is not supported", "the Schur complement needs Common->useGPU",
+    "the Schur complement runs on one rank only", NULL, NULL } ;
 
 /* what the three entry points ask of L and m; TRUE: L->hip_plan holds its numeric, positive definite factor */
-static int sc_factor_ready (cholmod_factor *L, size_t m, cholmod_common *Common)
+static int sc_ready (cholmod_factor *L, size_t m, cholmod_common *Common)
 {
-    if (L->xtype == CHOLMOD_COMPLEX || L->xtype == CHOLMOD_ZOMPLEX)
-    { ERROR (CHOLMOD_NOT_INSTALLED, "the Schur complement of a complex factor is not supported") ; return FALSE ; }
-    if (L->xtype != CHOLMOD_REAL || !L->is_super)
-    { ERROR (CHOLMOD_INVALID, "L must be a numeric supernodal factor") ; return FALSE ; }
-    if (m > L->n) { ERROR (CHOLMOD_INVALID, "m is larger than n") ; return FALSE ; }
-    if (L->minor < L->n) { ERROR (CHOLMOD_INVALID, "L is not positive definite") ; return FALSE ; }
-    /* formed from the factor in device memory: no fallback, whatever Common->hip_cpu_fallback says */
-    if (ssamd_resolve_use_gpu (Common) != 1) { ERROR (CHOLMOD_INVALID, "the Schur complement needs Common->useGPU") ; return FALSE ; }
-    if (Common->hip_world > 1) { ERROR (CHOLMOD_INVALID, "the Schur complement runs on one rank only") ; return FALSE ; }
-    if (!L->hip_plan || !L->hip_on_device)
-    { ERROR (CHOLMOD_INVALID, "L was not factorized on the device") ; return FALSE ; }
-    return TRUE ;
-}
-
-/* L->Perm to the plan on first use, as cholmod_l_hip_solve_device does */
-static int sc_perm_ready (cholmod_factor *L, cholmod_common *Common)
-{
-    if (L->hip_perm_set) return TRUE ;
-    int rc = cholmod_hip_set_perm ((cholmod_hip_plan *) L->hip_plan, (const int64_t *) L->Perm) ;
-    if (rc != CHOLMOD_HIP_OK) return sc_status (rc, Common, "the permutation could not be stored on the device") ;
-    L->hip_perm_set = TRUE ;
-    return TRUE ;
+    /* (a wrong kind of L is reported before a wrong m, a wrong m before the rest of the gate) */
+    if (L->xtype == CHOLMOD_REAL && L->is_super && m > L->n) { ERROR (CHOLMOD_INVALID, "m is larger than n") ; return FALSE ; }
+    return ssamd_resident_factor_ready (L, &schur_feature, TRUE, Common) ;
 }
 
 int cholmod_l_hip_schur_device (cholmod_factor *L, size_t m, double *S_dev, size_t lds, double *F_dev, size_t ldf,
@@ -50,11 +24,11 @@ int cholmod_l_hip_schur_device (cholmod_factor *L, size_t m, double *S_dev, size
     RETURN_IF_NULL_COMMON (FALSE) ;
     RETURN_IF_NULL (L, FALSE) ;
     if (!S_dev && !F_dev) { ERROR (CHOLMOD_INVALID, "argument missing") ; return FALSE ; }
-    if (!sc_factor_ready (L, m, Common)) return FALSE ;
+    if (!sc_ready (L, m, Common)) return FALSE ;
     if ((S_dev && lds < m) || (F_dev && ldf < m)) { ERROR (CHOLMOD_INVALID, "leading dimension smaller than m") ; return FALSE ; }
     Common->status = CHOLMOD_OK ;
     if (m == 0) return TRUE ;
-    return sc_status (cholmod_hip_schur_device ((cholmod_hip_plan *) L->hip_plan, (int64_t) m, S_dev, (int64_t) lds, F_dev,
+    return ssamd_device_status (cholmod_hip_schur_device ((cholmod_hip_plan *) L->hip_plan, (int64_t) m, S_dev, (int64_t) lds, F_dev,
         (int64_t) ldf, stream), Common, "the Schur complement could not be formed on the device") ;
 }
 
@@ -66,19 +40,19 @@ int cholmod_l_hip_schur_reduce_device (cholmod_factor *L, size_t m, const double
     RETURN_IF_NULL (B_dev, FALSE) ;
     RETURN_IF_NULL (Y_dev, FALSE) ;
     RETURN_IF_NULL (G_dev, FALSE) ;
-    if (!sc_factor_ready (L, m, Common)) return FALSE ;
+    if (!sc_ready (L, m, Common)) return FALSE ;
     if (ldb < L->n || ldy < L->n) { ERROR (CHOLMOD_INVALID, "leading dimension smaller than n") ; return FALSE ; }
     if (ldg < m) { ERROR (CHOLMOD_INVALID, "leading dimension smaller than m") ; return FALSE ; }
     Common->status = CHOLMOD_OK ;
     if (m == 0 || nrhs == 0) return TRUE ;
-    if (!sc_perm_ready (L, Common)) return FALSE ;
+    if (!ssamd_perm_ready (L, Common)) return FALSE ;
     cholmod_hip_plan *plan = (cholmod_hip_plan *) L->hip_plan ;
     const int64_t n = (int64_t) L->n ;
     /* Y = inv (L) P B, in the factor's ordering */
     int rc = cholmod_hip_solve_device (plan, 1, 1, 0, B_dev, (int64_t) ldb, Y_dev, (int64_t) ldy, (int64_t) nrhs, stream) ;
-    if (rc != CHOLMOD_HIP_OK) return sc_status (rc, Common, "HIP device solve failed") ;
+    if (rc != CHOLMOD_HIP_OK) return ssamd_device_status (rc, Common, "HIP device solve failed") ;
     /* G = L22 Y_S */
-    return sc_status (cholmod_hip_trailing_multiply_device (plan, (int64_t) m, 0, Y_dev + (n - (int64_t) m), (int64_t) ldy, G_dev,
+    return ssamd_device_status (cholmod_hip_trailing_multiply_device (plan, (int64_t) m, 0, Y_dev + (n - (int64_t) m), (int64_t) ldy, G_dev,
         (int64_t) ldg, (int64_t) nrhs, stream), Common, "the condensed right-hand side could not be formed on the device") ;
 }
 
@@ -90,25 +64,25 @@ int cholmod_l_hip_schur_expand_device (cholmod_factor *L, size_t m, const double
     RETURN_IF_NULL (Y_dev, FALSE) ;
     RETURN_IF_NULL (XS_dev, FALSE) ;
     RETURN_IF_NULL (X_dev, FALSE) ;
-    if (!sc_factor_ready (L, m, Common)) return FALSE ;
+    if (!sc_ready (L, m, Common)) return FALSE ;
     if (ldy < L->n || ldx < L->n) { ERROR (CHOLMOD_INVALID, "leading dimension smaller than n") ; return FALSE ; }
     if (ldxs < m) { ERROR (CHOLMOD_INVALID, "leading dimension smaller than m") ; return FALSE ; }
     if ((const double *) X_dev == Y_dev) { ERROR (CHOLMOD_INVALID, "X_dev and Y_dev must differ") ; return FALSE ; }
     Common->status = CHOLMOD_OK ;
     if (nrhs == 0 || L->n == 0) return TRUE ;
-    if (!sc_perm_ready (L, Common)) return FALSE ;
+    if (!ssamd_perm_ready (L, Common)) return FALSE ;
     cholmod_hip_plan *plan = (cholmod_hip_plan *) L->hip_plan ;
     const int64_t n = (int64_t) L->n ;
     /* W = [Y_I ; L22' XS], built in X_dev: all of Y first (a plain copy), then its last m rows overwritten ... */
     int rc = cholmod_hip_solve_device (plan, 3, 0, 0, Y_dev, (int64_t) ldy, X_dev, (int64_t) ldx, (int64_t) nrhs, stream) ;
-    if (rc != CHOLMOD_HIP_OK) return sc_status (rc, Common, "HIP device copy failed") ;
+    if (rc != CHOLMOD_HIP_OK) return ssamd_device_status (rc, Common, "HIP device copy failed") ;
     if (m > 0)
     {
         rc = cholmod_hip_trailing_multiply_device (plan, (int64_t) m, 1, XS_dev, (int64_t) ldxs, X_dev + (n - (int64_t) m),
             (int64_t) ldx, (int64_t) nrhs, stream) ;
-        if (rc != CHOLMOD_HIP_OK) return sc_status (rc, Common, "the interface solution could not be applied on the device") ;
+        if (rc != CHOLMOD_HIP_OK) return ssamd_device_status (rc, Common, "the interface solution could not be applied on the device") ;
     }
     /* ... X = P' inv (L') W, in place (the sweeps run on the engine's own panel).  m == 0: the plain L' solve of Y. */
-    return sc_status (cholmod_hip_solve_device (plan, 2, 0, 1, X_dev, (int64_t) ldx, X_dev, (int64_t) ldx, (int64_t) nrhs, stream),
+    return ssamd_device_status (cholmod_hip_solve_device (plan, 2, 0, 1, X_dev, (int64_t) ldx, X_dev, (int64_t) ldx, (int64_t) nrhs, stream),
         Common, "HIP device solve failed") ;
 }
