@@ -257,7 +257,7 @@ int cholmod_hip_factorize_resident (cholmod_hip_plan *plan, double beta,
  * fills the buffer chunk by chunk (*chunk_len positions, a multiple of 32768) and calls
  * cholmod_hip_values_push_chunk (c) for c = 0, 1, ... in order as each chunk is complete --
  * an asynchronous DMA -- or (-1) to cancel; cholmod_hip_factorize_resident, called once
- * after begin from any thread, waits for the chunks it needs (engine.hip has the protocol)
+ * after begin from any thread, waits for the chunks it needs (values.hip has the protocol)
  * and returns an error after a cancel. */
 int cholmod_hip_set_value_map (cholmod_hip_plan *plan, const int64_t *src, int64_t snz,
     int64_t nvalues) ;

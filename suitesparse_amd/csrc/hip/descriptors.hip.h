@@ -159,7 +159,7 @@ struct InvTask { i32 front ; i32 jb ; i64 w_off ; } ;
 struct SolveBlk { i32 front, jb, w, wg_start, inv, slot ; } ;   // inv: index of its first 64 x 64 inverse
 // factor checks
 #define CHK_COLS 64
-// the length classes of the product map's lists (k_product_values, kernels.hip.h) and of its transpose (k_product_grad,
+// the length classes of the product map's lists (k_product_values, values_kernels.hip.h) and of its transpose (k_product_grad,
 // grad_kernels.hip.h): up to PM_LEN1 pairs one lane owns a list, up to PM_LEN16 sixteen lanes, above that a wave
 #define PM_LEN1 8
 #define PM_LEN16 128

@@ -1,5 +1,5 @@
-// device_util.hip.h -- the few device helpers the factorization kernels (kernels.hip.h) and the solve kernels
-// (solve_kernels.hip.h) share: the vector types, the access to a complex factor in its own storage, a binary search
+// device_util.hip.h -- the few device helpers the factorization kernels (kernels.hip.h), the solve kernels
+// (solve_kernels.hip.h) and the check kernels (check_kernels.hip.h) share: the vector types, the access to a complex factor in its own storage, a binary search
 // and two lane exchanges.  Inline code only, so that several objects of one library may include it.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,26 +1,14 @@
 // engine.hip -- host side of the MI355X supernodal Cholesky engine that touches the device: upload of a plan
 // (plan_build.hip / schedule_dense.hip derive it), the runner of its launch list, and the extern "C" shim declared in
-// include/cholmod_hip.h (the exchange between ranks and the gather: exchange.hip; the triangular solves: solve.hip).
-// One process drives one GPU.
+// include/cholmod_hip.h (the exchange between ranks and the gather: exchange.hip; the triangular solves: solve.hip; the
+// matrix-values pipeline: values.hip; the checks on a finished factor: checks.hip).  One process drives one GPU.
 #include "update_launch.hip.h"
 #include "chain256_kernels.hip.h"
 #include "exchange_internal.hip.h"
+#include "engine_internal.hip.h"
 #include <thread>
 
 namespace {
-
-/* the product map of the value map goes with it (cholmod_hip_set_product_map) */
-static void drop_product_map (cholmod_hip_plan *P)
-{
-    for (void *d : {(void *) P->d_pm_cp, (void *) P->d_pm_ia, (void *) P->d_pm_ib, (void *) P->d_pm_order}) if (d) (void) hipFree (d) ;
-    P->d_pm_cp = P->d_pm_ia = P->d_pm_ib = nullptr ; P->d_pm_order = nullptr ;
-    P->pm_set = false ; P->pm_na = 0 ;
-    /* ... and its transpose, where a gradient call has built it (grad.hip) */
-    for (void *d : {(void *) P->d_pt_ptr, (void *) P->d_pt_c, (void *) P->d_pt_partner, (void *) P->d_pt_order, (void *) P->d_pt_gvals})
-        if (d) (void) hipFree (d) ;
-    P->d_pt_ptr = nullptr ; P->d_pt_c = P->d_pt_partner = P->d_pt_order = nullptr ; P->d_pt_gvals = nullptr ;
-    P->pt_built = false ;
-}
 
 static void free_device (cholmod_hip_plan *P)
 {
@@ -230,11 +218,9 @@ static int thin_minw (int cls) { return cls == 2 ? 3 : 4 ; }
 static int run_launch (cholmod_hip_plan *P, const Launch &L, bool serial)
 {
     hipStream_t st = (serial || L.stream == 0 || !P->stream2) ? P->stream : P->stream2 ;
-    const bool cx = (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;      // a complex factor in its own storage (kernels.hip.h: ldcx / stcx)
-    const bool twin = !cx && (P->flags & CHOLMOD_HIP_PHI_TWIN) != 0 ;      // update kernels contract over the even columns
-// K<true> for a complex factor in its own storage, K<false> otherwise
-#define CX_LAUNCH(K, ...) do { if (cx) hipLaunchKernelGGL (K<true>, __VA_ARGS__) ; else hipLaunchKernelGGL (K<false>, __VA_ARGS__) ; } while (0)
-    const int tw = cx ? 2 : twin ? 1 : 0 ;                          // the update kernels' TW (update_launch.hip.h: with_tw)
+    const bool cxs = (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;     // a complex factor in its own storage (device_util.hip.h: ldcx / stcx; CXS_LAUNCH)
+    const bool twin = !cxs && (P->flags & CHOLMOD_HIP_PHI_TWIN) != 0 ;     // update kernels contract over the even columns
+    const int tw = cxs ? 2 : twin ? 1 : 0 ;                         // the update kernels' TW (update_launch.hip.h: with_tw)
     // (test hook CHOLMOD_HIP_TEST_DROP_WAITS=1: the cross-stream waits of the schedule are skipped -- the mutation the jitter
     // test must catch, tests/test_gpu_scale.py::test_stream_jitter_catches_a_dropped_wait; =2: only the joins with the far-row
     // gathers of the shared fronts, tests/test_dist.py)
@@ -272,7 +258,7 @@ static int run_launch (cholmod_hip_plan *P, const Launch &L, bool serial)
                     P->s_unpacked ? P->d_Snz : nullptr, P->d_Si, P->d_Sx, P->cur_beta, \
                     P->d_Lx, P->d_cb, P->d_info, L.aux, P->d_amap, P->cur_mapped, (TIMED_) ? tim : (long long *) nullptr)
                 // complex storage: one wave per front up to 64 twin rows, four above
-                if (cx) { if (L.aux > 64) THIN_LAUNCH (4, false, 2, true) ; else THIN_LAUNCH (1, false, 4, true) ; }
+                if (cxs) { if (L.aux > 64) THIN_LAUNCH (4, false, 2, true) ; else THIN_LAUNCH (1, false, 4, true) ; }
                 else if (L.leaf_pw && P->cur_mapped && !P->s_unpacked && !tim)
                 {
                     // leaf fronts two to a wave, once the assembly map of the resident S exists
@@ -317,24 +303,24 @@ static int run_launch (cholmod_hip_plan *P, const Launch &L, bool serial)
             hipLaunchKernelGGL (k_zero, dim3 (L.grid), dim3 (256), 0, st,
                 P->d_zg + L.goff, L.ng, P->d_cb) ; break ;
         case K_EA:
-            CX_LAUNCH (k_extend_add, dim3 (L.grid), dim3 (L.stream == 1 && !serial && narrow_xs () ? 64 : 256), 0, st,
+            CXS_LAUNCH (k_extend_add, dim3 (L.grid), dim3 (L.stream == 1 && !serial && narrow_xs () ? 64 : 256), 0, st,
                 P->d_eg + L.goff, L.ng, P->d_fr, P->d_child, P->d_crel, P->d_relmap, P->d_Lx, P->d_cb, L.aux > 0 ? L.aux : EA_TW) ; break ;
         case K_POTRF:
-            if (cx) hipLaunchKernelGGL ((k_potrf_mfma<false, true>), dim3 (L.grid), dim3 (256), 0, st,
+            if (cxs) hipLaunchKernelGGL ((k_potrf_mfma<false, true>), dim3 (L.grid), dim3 (256), 0, st,
                 P->d_pg + L.goff, P->d_Lx, P->d_info, (long long *) nullptr) ;
             else hipLaunchKernelGGL ((k_potrf_mfma<false, false>), dim3 (L.grid), dim3 (256), 0, st,
                 P->d_pg + L.goff, P->d_Lx, P->d_info, (long long *) nullptr) ;
             break ;
         case K_TRSM:
             { int rl = raise_lds_limits () ; if (rl != CHOLMOD_HIP_OK) return rl ; }
-            if (cx) hipLaunchKernelGGL ((k_trsm_mfma<false, true>), dim3 (L.grid), dim3 (256), trsm_mfma_lds_bytes (L.aux), st,
+            if (cxs) hipLaunchKernelGGL ((k_trsm_mfma<false, true>), dim3 (L.grid), dim3 (256), trsm_mfma_lds_bytes (L.aux), st,
                 P->d_tg + L.goff, L.ng, P->d_Lx, P->d_info, L.aux, (long long *) nullptr) ;
             else hipLaunchKernelGGL ((k_trsm_mfma<false, false>), dim3 (L.grid), dim3 (256), trsm_mfma_lds_bytes (L.aux), st,
                 P->d_tg + L.goff, L.ng, P->d_Lx, P->d_info, L.aux, (long long *) nullptr) ;
             break ;
         case K_TRSM_UPD:
             { int rl = raise_lds_limits () ; if (rl != CHOLMOD_HIP_OK) return rl ; }
-            CX_LAUNCH (k_trsm_upd, dim3 (L.grid), dim3 (256), trsm_upd_lds_bytes (), st,
+            CXS_LAUNCH (k_trsm_upd, dim3 (L.grid), dim3 (256), trsm_upd_lds_bytes (), st,
                 P->d_tg + L.goff, L.ng, P->d_Lx, P->d_info, P->d_tu_cnt + L.goff) ;
             break ;
         case K_UPD_BIG:
@@ -397,7 +383,6 @@ static int wait_pushed (cholmod_hip_plan *P, long c)
     }
 }
 
-// Run the numeric factorization on the resident S.  Leaves Lx on the device.
 /* the chunks 0 .. need-1 into S and L, on the main stream, as soon as each has been pushed and copied */
 static int apply_value_chunks (cholmod_hip_plan *P, long need)
 {
@@ -415,10 +400,15 @@ static int apply_value_chunks (cholmod_hip_plan *P, long need)
     return CHOLMOD_HIP_OK ;
 }
 
+} // namespace
+
+// what values.hip calls (engine_internal.hip.h)
+namespace sship {
+
 /* What a factorization enqueues before it touches a value: the start event, (re)allocation of what a gather released, the
  * clearing of L and of the per-factorization counters.  cholmod_hip_values_begin calls it ahead of time, so that the
  * clearing runs beside the upload of the values. */
-static int factorize_prologue (cholmod_hip_plan *P)
+int factorize_prologue (cholmod_hip_plan *P)
 {
     hipStream_t st = P->stream ;
     P->winv_valid = false ;                 // the diagonal-block inverses follow the factor
@@ -465,9 +455,11 @@ static int factorize_prologue (cholmod_hip_plan *P)
     return CHOLMOD_HIP_OK ;
 }
 
-static int run_factorize (cholmod_hip_plan *P, double beta, int quick, i64 *minor)
+// Run the numeric factorization on the resident S.  Leaves Lx on the device.
+int run_factorize (cholmod_hip_plan *P, double beta, int quick, i64 *minor)
 {
     hipStream_t st = P->stream ;
+    const bool cxs = (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;
     if (!P->d_Sp) return CHOLMOD_HIP_INVALID ;
     bool prof = P->profiling ;
     static const bool host_timing = getenv ("CHOLMOD_HIP_HOST_TIMING") != nullptr ;
@@ -516,20 +508,13 @@ static int run_factorize (cholmod_hip_plan *P, double beta, int quick, i64 *mino
             hipLaunchKernelGGL (k_assemble_mapped, dim3 ((unsigned) ((P->s_nz + 255) / 256)), dim3 (256), 0, st,
                 P->s_nz, P->d_amap, P->d_Sx, P->d_Lx) ;
         if (beta != 0.0)
-        {
-            if (P->flags & CHOLMOD_HIP_CX_STORAGE) hipLaunchKernelGGL (k_add_beta<true>, dim3 ((unsigned) ((P->n + 255) / 256)), dim3 (256), 0, st,
+            CXS_LAUNCH (k_add_beta, dim3 ((unsigned) ((P->n + 255) / 256)), dim3 (256), 0, st,
                 P->n, P->d_supermap, P->d_fr, P->d_Lx, beta) ;
-            else hipLaunchKernelGGL (k_add_beta<false>, dim3 ((unsigned) ((P->n + 255) / 256)), dim3 (256), 0, st,
-                P->n, P->d_supermap, P->d_fr, P->d_Lx, beta) ;
-        }
     }
     else if (P->n > 0)
     {
         HIPCHK (hipMemsetAsync (P->d_amap, 0xFF, std::max<i64> (P->s_nz, 1) * sizeof (i64), st)) ;     // -1: not in L
-        if (P->flags & CHOLMOD_HIP_CX_STORAGE) hipLaunchKernelGGL (k_assemble<true>, dim3 ((unsigned) ((P->n + 255) / 256)), dim3 (256), 0, st,
-            P->n, P->d_Sp, P->s_unpacked ? P->d_Snz : nullptr, P->d_Si, P->d_Sx,
-            P->d_supermap, P->d_fr, P->d_Ls, P->d_Lx, beta, P->d_amap) ;
-        else hipLaunchKernelGGL (k_assemble<false>, dim3 ((unsigned) ((P->n + 255) / 256)), dim3 (256), 0, st,
+        CXS_LAUNCH (k_assemble, dim3 ((unsigned) ((P->n + 255) / 256)), dim3 (256), 0, st,
             P->n, P->d_Sp, P->s_unpacked ? P->d_Snz : nullptr, P->d_Si, P->d_Sx,
             P->d_supermap, P->d_fr, P->d_Ls, P->d_Lx, beta, P->d_amap) ;
         building_map = true ;       // (the thin-front kernels record their part; valid once every launch has run)
@@ -696,7 +681,7 @@ static int run_factorize (cholmod_hip_plan *P, double beta, int quick, i64 *mino
     return CHOLMOD_HIP_NOT_POSDEF ;
 }
 
-} // namespace
+} // namespace sship
 
 // ============================================================================
 // extern "C" shim
@@ -908,222 +893,6 @@ void cholmod_hip_plan_destroy (cholmod_hip_plan *P)
     delete P ;
 }
 
-int cholmod_hip_upload_matrix (cholmod_hip_plan *P, const int64_t *Sp, const int64_t *Si,
-    const int64_t *Snz, const double *Sx)
-{
-    if (!P || P->host_only || !Sp || !Si || !Sx) return CHOLMOD_HIP_INVALID ;
-    i64 n = P->n ;
-    i64 nz = 0 ;
-    if (Snz) { for (i64 j = 0 ; j < n ; j++) nz = std::max<i64> (nz, Sp [j] + Snz [j]) ; }
-    else nz = Sp [n] ;
-    if (nz > P->s_nz || !P->d_Sp)
-    {
-        if (P->d_Sp) { (void) hipFree (P->d_Sp) ; (void) hipFree (P->d_Si) ; (void) hipFree (P->d_Sx) ; (void) hipFree (P->d_Snz) ; (void) hipFree (P->d_amap) ; }
-        P->d_Sp = P->d_Si = P->d_Snz = P->d_amap = nullptr ; P->d_Sx = nullptr ;
-        HIPCHK (hipMalloc ((void **) &P->d_Sp, (n + 1) * sizeof (i64))) ;
-        HIPCHK (hipMalloc ((void **) &P->d_Snz, std::max<i64> (n, 1) * sizeof (i64))) ;
-        HIPCHK (hipMalloc ((void **) &P->d_Si, std::max<i64> (nz, 1) * sizeof (i64))) ;
-        HIPCHK (hipMalloc ((void **) &P->d_Sx, std::max<i64> (nz, 1) * sizeof (double))) ;
-        HIPCHK (hipMalloc ((void **) &P->d_amap, std::max<i64> (nz, 1) * sizeof (i64))) ;
-        P->s_nz = nz ;
-    }
-    HIPCHK (hipMemcpyAsync (P->d_Sp, Sp, (n + 1) * sizeof (i64), hipMemcpyHostToDevice, P->stream)) ;
-    if (Snz) HIPCHK (hipMemcpyAsync (P->d_Snz, Snz, n * sizeof (i64), hipMemcpyHostToDevice, P->stream)) ;
-    if (nz) HIPCHK (hipMemcpyAsync (P->d_Si, Si, nz * sizeof (i64), hipMemcpyHostToDevice, P->stream)) ;
-    if (nz) HIPCHK (hipMemcpyAsync (P->d_Sx, Sx, nz * sizeof (double), hipMemcpyHostToDevice, P->stream)) ;
-    if (!P->sch.sm.empty ())
-    {
-        // the range of S every thin front's columns occupy, in the block order of its launch
-        std::vector<i64> sp01 (2 * P->sch.sm.size ()) ;
-        for (size_t q = 0 ; q < P->sch.sm.size () ; q++)
-        {
-            const FrontD &f = P->fr [P->sch.sm [q]] ;
-            sp01 [2 * q] = Sp [f.k1] ; sp01 [2 * q + 1] = Sp [f.k1 + f.nscol] ;
-        }
-        HIPCHK (hipMemcpyAsync (P->d_sp01, sp01.data (), sp01.size () * sizeof (i64), hipMemcpyHostToDevice, P->stream)) ;
-        HIPCHK (hipStreamSynchronize (P->stream)) ;     // (sp01 is a local)
-    }
-    HIPCHK (hipStreamSynchronize (P->stream)) ;
-    P->s_unpacked = (Snz != nullptr) ;
-    P->amap_valid = false ;         // a new pattern may have come with the new values
-    P->rs_index_valid = false ;     // ... and the transposed index of the residual goes with the old one
-    P->gr_index_valid = false ;     // ... and the column-of-entry array of the gradient
-    P->si_valid = P->fg_valid = false ;         // ... and the selected inverse and the factor gradient are those of the old matrix
-    P->s_cur_nz = nz ;
-    P->vsrc_nz = 0 ;                // ... and the value map of the previous one is void
-    drop_product_map (P) ;          // ... with its product map
-    P->h_vgather.clear () ; P->nchunks = 0 ;
-    if (!Snz && P->world == 1) P->h_Sp.assign (Sp, Sp + n + 1) ; else P->h_Sp.clear () ;
-    return CHOLMOD_HIP_OK ;
-}
-
-int cholmod_hip_set_value_map (cholmod_hip_plan *P, const int64_t *src, int64_t snz, int64_t nvalues)
-{
-    if (!P || P->host_only || !src || !P->d_Sp || P->s_unpacked || snz != P->s_cur_nz || nvalues < 0) return CHOLMOD_HIP_INVALID ;
-    for (i64 q = 0 ; q < snz ; q++) if (src [q] < 0 || src [q] >= nvalues) return CHOLMOD_HIP_INVALID ;
-    drop_product_map (P) ;          // (a product map describes the values of ONE value map)
-    if (P->d_vsrc) { (void) hipFree (P->d_vsrc) ; P->d_vsrc = nullptr ; }
-    if (P->d_vals) { (void) hipFree (P->d_vals) ; P->d_vals = nullptr ; }
-    HIPCHK (hipMalloc ((void **) &P->d_vsrc, std::max<i64> (snz, 1) * sizeof (i64))) ;
-    HIPCHK (hipMalloc ((void **) &P->d_vals, std::max<i64> (nvalues, 1) * sizeof (double))) ;
-    if (snz) HIPCHK (hipMemcpy (P->d_vsrc, src, snz * sizeof (i64), hipMemcpyHostToDevice)) ;
-    P->vsrc_nz = snz ; P->vals_n = nvalues ;
-    // the same map in the order the factorization asks for the values: entries of S sorted by the LAUNCH that needs them
-    // first -- a thin front's entries by its own launch (the thin-front kernels read their columns of S themselves), a
-    // generic front's by the first launch of its batch behind the thin ones (k_values_chunk has then put them into L) --
-    // and by source position inside such a class.  One rank, packed S.
-    P->h_vgather.clear () ; P->launch_need_chunks.clear () ;
-    if (P->d_vorder) { (void) hipFree (P->d_vorder) ; P->d_vorder = nullptr ; }
-    static const bool chunked_off = getenv ("CHOLMOD_HIP_VALUES_IN_BATCH_ORDER") && !strcmp (getenv ("CHOLMOD_HIP_VALUES_IN_BATCH_ORDER"), "0") ;
-    if (!chunked_off && P->world == 1 && !(P->flags & CHOLMOD_HIP_CX_STORAGE) && (i64) P->h_Sp.size () == P->n + 1 && snz > 0 && snz <= nvalues
-        && !P->batch_launch0.empty () && !P->force_shared)
-    {
-        const size_t nb = P->batch_launch0.size (), nl = P->sch.launches.size () ;
-        // need [sf]: the launch before which front sf's entries must have been applied
-        std::vector<i32> need ((size_t) std::max<i64> (P->nsuper, 1), -1) ;
-        std::vector<i32> generic_launch (nb, 0) ;
-        bool okn = true ;
-        for (size_t b = 0 ; b < nb ; b++)
-        {
-            const size_t q0 = P->batch_launch0 [b], q1 = (b + 1 < nb) ? P->batch_launch0 [b + 1] : nl ;
-            size_t q = q0 ;
-            for ( ; q < q1 && P->sch.launches [q].kind == K_SMALL ; q++)
-            {
-                const Launch &Lq = P->sch.launches [q] ;
-                for (size_t e = Lq.goff ; e < Lq.goff + (size_t) Lq.ng ; e++) need [P->sch.sm [e]] = (i32) q ;
-            }
-            generic_launch [b] = (i32) std::min (q, q1 > 0 ? q1 - 1 : 0) ;
-        }
-        for (i64 sf = 0 ; sf < P->nsuper && okn ; sf++)
-        {
-            const i32 b = P->batch_of [sf] ;
-            if (b < 0 || (size_t) b >= nb) { okn = false ; break ; }
-            if (need [sf] < 0) need [sf] = generic_launch [b] ;
-        }
-        if (okn && nl > 0)
-        {
-            // buckets by need, filled in source order on a few threads: the caller's staging copy (stage [k] = values
-            // [index [k]]) then walks its value array front to back once per class -- sequential reads with gaps -- and the
-            // scatter to S's order is left to the device, where it costs nothing.  (S's own order made that copy a random
-            // gather: 1.7 ms for the 4.75 M entries of the 2D stand-in against 0.4 ms for a plain copy.)
-            std::vector<i64> order ((size_t) snz) ;
-            P->h_vgather.resize ((size_t) snz) ;
-            std::vector<i64> cnt (nl + 1, 0) ;
-            {
-                std::vector<i32> needq ((size_t) snz) ;
-                std::vector<i64> inv ((size_t) nvalues, -1) ;
-                const int T = (int) std::max<i64> (1, std::min<i64> (8, snz / 200000)) ;
-                auto par = [&] (auto fn) {
-                    std::vector<std::thread> th ;
-                    for (int t = 1 ; t < T ; t++) th.emplace_back (fn, t) ;
-                    fn (0) ;
-                    for (auto &x : th) x.join () ;
-                } ;
-                par ([&] (int t) {
-                    const i64 s0 = P->nsuper * t / T, s1 = P->nsuper * (t + 1) / T ;
-                    for (i64 sf = s0 ; sf < s1 ; sf++)
-                        for (i64 q = P->h_Sp [P->super [sf]] ; q < P->h_Sp [P->super [sf + 1]] ; q++) { needq [q] = need [sf] ; inv [src [q]] = q ; }
-                }) ;
-                std::vector<std::vector<i64>> tcnt (T, std::vector<i64> (nl, 0)) ;
-                par ([&] (int t) {
-                    const i64 a0 = nvalues * t / T, a1 = nvalues * (t + 1) / T ;
-                    for (i64 a = a0 ; a < a1 ; a++) if (inv [a] >= 0) tcnt [t][needq [inv [a]]]++ ;
-                }) ;
-                for (size_t q = 0 ; q < nl ; q++)
-                {
-                    i64 off = cnt [q] ;
-                    for (int t = 0 ; t < T ; t++) { const i64 c = tcnt [t][q] ; tcnt [t][q] = off ; off += c ; }
-                    cnt [q + 1] = off ;
-                }
-                par ([&] (int t) {
-                    const i64 a0 = nvalues * t / T, a1 = nvalues * (t + 1) / T ;
-                    for (i64 a = a0 ; a < a1 ; a++)
-                    {
-                        const i64 q = inv [a] ;
-                        if (q < 0) continue ;
-                        const i64 k = tcnt [t][needq [q]]++ ;
-                        order [k] = q ; P->h_vgather [k] = a ;
-                    }
-                }) ;
-            }
-            HIPCHK (hipMalloc ((void **) &P->d_vorder, (size_t) snz * sizeof (i64))) ;
-            HIPCHK (hipMemcpy (P->d_vorder, order.data (), (size_t) snz * sizeof (i64), hipMemcpyHostToDevice)) ;
-            // chunks a launch needs = those that hold the entries of every class up to its own
-            P->launch_need_chunks.assign (nl + 1, (i32) ((snz + P->chunk_len - 1) / P->chunk_len)) ;
-            for (size_t q = 0 ; q < nl ; q++) P->launch_need_chunks [q] = (i32) ((cnt [q + 1] + P->chunk_len - 1) / P->chunk_len) ;
-        }
-    }
-    return CHOLMOD_HIP_OK ;
-}
-
-/* The value upload of a call with the pattern of the resident S (cholmod_l_factorize), driven by the caller's threads:
- *   * cholmod_hip_values_begin: the plan's pinned staging buffer, and where staged position k comes from in the caller's
- *     value array -- in batch order (the entries of S sorted by the launch that first needs them, set_value_map above) --
- *     or NULL: in S order, the caller's array as it is.  The clearing of L is enqueued at once (it runs beside the
- *     upload), the chunk counters are reset;
- *   * cholmod_hip_factorize_resident follows.  In batch order its launch loop waits -- host side for the push, device side
- *     for the copy -- only for the chunks the next batch needs, applies them (k_values_chunk) and goes on; in S order
- *     every launch needs every value: it waits for the last push, whose gather into S the assembly waits for on the device;
- *   * cholmod_hip_values_push_chunk (plan, c) for c = 0, 1, ... as chunks are staged (one thread, in order; a DMA on the
- *     exchange stream, no host wait); (plan, -1) cancels: the waiting factorization returns an error.
- * Nothing of this touches the resident S before the factorization's turn. */
-int cholmod_hip_values_begin (cholmod_hip_plan *P, double **buffer, const int64_t **index, int64_t *count, int64_t *chunk_len)
-{
-    if (!P || P->host_only || !buffer || !index || !count || !chunk_len || !P->d_vsrc || P->vsrc_nz != P->s_cur_nz)
-        return CHOLMOD_HIP_INVALID ;
-    const bool batch = !P->h_vgather.empty () && (i64) P->h_vgather.size () == P->s_cur_nz && P->amap_valid && P->d_vorder
-        && P->launch_need_chunks.size () == P->sch.launches.size () + 1 ;
-    if (!P->h_vals || P->h_vals_n != P->vals_n)
-    {
-        if (P->h_vals) { (void) hipHostFree (P->h_vals) ; P->h_vals = nullptr ; }
-        if (hipHostMalloc ((void **) &P->h_vals, (size_t) std::max<i64> (P->vals_n, 1) * sizeof (double), hipHostMallocDefault) != hipSuccess)
-        {
-            (void) hipGetLastError () ;
-            P->h_vals = nullptr ;
-            return CHOLMOD_HIP_OUT_OF_MEMORY ;
-        }
-        P->h_vals_n = P->vals_n ;
-    }
-    const i64 staged = batch ? P->s_cur_nz : P->vals_n ;
-    P->nchunks = (long) ((staged + P->chunk_len - 1) / P->chunk_len) ;
-    while ((long) P->chunk_ev.size () < P->nchunks)
-    {
-        hipEvent_t e ; HIPCHK (hipEventCreateWithFlags (&e, hipEventDisableTiming)) ; P->chunk_ev.push_back (e) ;
-    }
-    const int rc = factorize_prologue (P) ;
-    if (rc != CHOLMOD_HIP_OK) return rc ;
-    P->chunks_pushed.store (0) ;
-    P->chunks_applied = 0 ;
-    P->values_begun = true ;
-    P->values_in_batch_order = batch ;
-    *buffer = P->h_vals ; *index = batch ? P->h_vgather.data () : nullptr ;
-    *count = staged ; *chunk_len = P->chunk_len ;
-    return CHOLMOD_HIP_OK ;
-}
-
-int cholmod_hip_values_push_chunk (cholmod_hip_plan *P, int64_t c)
-{
-    if (!P || !P->h_vals) return CHOLMOD_HIP_INVALID ;
-    if (c < 0 || c >= P->nchunks) { P->chunks_pushed.store (-1) ; return CHOLMOD_HIP_INVALID ; }
-    const bool s_order = !P->values_in_batch_order ;
-    const i64 k0 = c * P->chunk_len, k1 = std::min<i64> (k0 + P->chunk_len, s_order ? P->vals_n : P->s_cur_nz) ;
-    bool ok = hipMemcpyAsync (P->d_vals + k0, P->h_vals + k0, (size_t) (k1 - k0) * sizeof (double), hipMemcpyHostToDevice, P->stream2) == hipSuccess ;
-    if (ok && s_order && c == P->nchunks - 1 && P->vsrc_nz > 0)
-    {
-        hipLaunchKernelGGL (k_gather_values, dim3 ((unsigned) ((P->vsrc_nz + 255) / 256)), dim3 (256), 0, P->stream2,
-            P->vsrc_nz, P->d_vsrc, P->d_vals, P->d_Sx) ;
-        ok = hipGetLastError () == hipSuccess ;
-    }
-    if (!ok || hipEventRecord (P->chunk_ev [c], P->stream2) != hipSuccess)
-    {
-        (void) hipGetLastError () ;
-        P->chunks_pushed.store (-1) ;
-        return CHOLMOD_HIP_GPU_PROBLEM ;
-    }
-    P->chunks_pushed.store ((long) c + 1, std::memory_order_release) ;
-    return CHOLMOD_HIP_OK ;
-}
-
 int cholmod_hip_factorize_resident (cholmod_hip_plan *P, double beta,
     int quick_return_if_not_posdef, int64_t *minor)
 {
@@ -1132,94 +901,6 @@ int cholmod_hip_factorize_resident (cholmod_hip_plan *P, double beta,
     int rc = run_factorize (P, beta, quick_return_if_not_posdef, &m) ;
     if (minor) *minor = m ;
     return rc ;
-}
-
-/* The values of the value map as sums of products of the caller's values (cholmod_hip.h): validated here, entry by
- * entry, so that k_product_values needs no bounds check of its own; then the lists go up once, with the entries sorted
- * by list length into the kernel's three classes (a counting sort: inside a class the entries keep their order). */
-int cholmod_hip_set_product_map (cholmod_hip_plan *P, const int64_t *cp, const int64_t *ia, const int64_t *ib,
-    int64_t nc, int64_t navalues)
-{
-    if (!P || P->host_only) return CHOLMOD_HIP_INVALID ;
-    if (!cp) { drop_product_map (P) ; return CHOLMOD_HIP_OK ; }
-    if (!ia || !ib || !P->d_vsrc || P->vsrc_nz != P->s_cur_nz || nc != P->vals_n || nc < 0 || navalues < 0 || cp [0] != 0)
-        return CHOLMOD_HIP_INVALID ;
-    for (i64 c = 0 ; c < nc ; c++) if (cp [c + 1] < cp [c]) return CHOLMOD_HIP_INVALID ;
-    const i64 np = cp [nc] ;
-    if (np > INT32_MAX || nc > INT32_MAX) return CHOLMOD_HIP_TOO_LARGE ;
-    for (i64 p = 0 ; p < np ; p++) if (ia [p] < 0 || ia [p] >= navalues || ib [p] < 0 || ib [p] >= navalues) return CHOLMOD_HIP_INVALID ;
-    drop_product_map (P) ;
-    auto cls = [&] (i64 c) { const i64 len = cp [c + 1] - cp [c] ; return len <= PM_LEN1 ? 0 : len <= PM_LEN16 ? 1 : 2 ; } ;
-    i64 first [4] = {0, 0, 0, 0} ;
-    for (i64 c = 0 ; c < nc ; c++) first [cls (c) + 1]++ ;
-    for (int k = 0 ; k < 3 ; k++) first [k + 1] += first [k] ;
-    std::vector<i32> order ((size_t) nc) ;
-    {
-        i64 next [3] = {first [0], first [1], first [2]} ;
-        for (i64 c = 0 ; c < nc ; c++) order [next [cls (c)]++] = (i32) c ;
-    }
-    const std::vector<i64> vcp (cp, cp + nc + 1), via (ia, ia + np), vib (ib, ib + np) ;
-    hipError_t e = hipSuccess ;
-    P->d_pm_cp = dupload (vcp, e) ;
-    if (e == hipSuccess) P->d_pm_ia = dupload (via, e) ;
-    if (e == hipSuccess) P->d_pm_ib = dupload (vib, e) ;
-    if (e == hipSuccess) P->d_pm_order = dupload (order, e) ;
-    if (e != hipSuccess)
-    {
-        const int rc = alloc_failure (e) ;
-        drop_product_map (P) ;
-        return rc ;
-    }
-    for (int k = 0 ; k < 4 ; k++) P->pm_class [k] = first [k] ;
-    P->pm_na = navalues ;
-    P->pm_set = true ;
-    return CHOLMOD_HIP_OK ;
-}
-
-/* A values-only factorization whose values are in device memory already (cholmod_hip.h): the engine stream takes its
- * place behind the caller's, the values go from dvalues straight into the resident S -- through the product kernel and the
- * plan's d_vals first when they are to be computed -- and the factorization runs as on any resident S: the assembly
- * (k_assemble_mapped, one value of S per entry of L) is the first to read them.  No pinned buffer, no copy. */
-int cholmod_hip_factorize_values_device (cholmod_hip_plan *P, const double *dvalues, int64_t nvalues,
-    double beta, int quick_return_if_not_posdef, void *stream, int64_t *minor)
-{
-    if (!real_device_plan (P) || !dvalues || !minor) return CHOLMOD_HIP_INVALID ;
-    if (!P->d_Sp || !P->d_vsrc || P->s_unpacked || P->vsrc_nz != P->s_cur_nz) return CHOLMOD_HIP_INVALID ;
-    if (nvalues != (P->pm_set ? P->pm_na : P->vals_n)) return CHOLMOD_HIP_INVALID ;
-    if (P->values_begun) return CHOLMOD_HIP_INVALID ;           // (a host upload is under way: its factorization comes first)
-    hipStream_t user = (hipStream_t) stream, st = P->stream ;
-    HIP_TRY (stream_enter (P, user)) ;
-    const double *vals = dvalues ;
-    if (P->pm_set)
-    {
-        const i64 *c = P->pm_class ;
-#define PM_LAUNCH(G_, K_) if (c [K_ + 1] > c [K_]) \
-            hipLaunchKernelGGL (k_product_values<G_>, dim3 ((unsigned) (((c [K_ + 1] - c [K_]) * G_ + 255) / 256)), dim3 (256), 0, st, \
-                c [K_ + 1] - c [K_], P->d_pm_order + c [K_], P->d_pm_cp, P->d_pm_ia, P->d_pm_ib, dvalues, P->d_vals)
-        PM_LAUNCH (1, 0) ; PM_LAUNCH (16, 1) ; PM_LAUNCH (64, 2) ;
-#undef PM_LAUNCH
-        vals = P->d_vals ;
-    }
-    if (P->vsrc_nz > 0)
-        hipLaunchKernelGGL (k_gather_values, dim3 ((unsigned) ((P->vsrc_nz + 255) / 256)), dim3 (256), 0, st,
-            P->vsrc_nz, P->d_vsrc, vals, P->d_Sx) ;
-    HIPCHK (hipGetLastError ()) ;
-    i64 m = P->n ;
-    const int rc = run_factorize (P, beta, quick_return_if_not_posdef, &m) ;
-    *minor = m ;
-    if (rc < 0) return rc ;
-    // (run_factorize has checked the launches and waited for the engine stream: what the caller enqueues next finds the
-    // factor, and dvalues is free)
-    HIP_TRY (stream_rejoin (P, user)) ;
-    return rc ;
-}
-
-int cholmod_hip_download_matrix_values (cholmod_hip_plan *P, double *Sx_host)
-{
-    if (!P || P->host_only || !Sx_host || !P->d_Sp || !P->d_Sx) return CHOLMOD_HIP_INVALID ;
-    HIPCHK (hipStreamSynchronize (P->stream)) ;
-    if (P->s_cur_nz > 0) HIPCHK (hipMemcpy (Sx_host, P->d_Sx, (size_t) P->s_cur_nz * sizeof (double), hipMemcpyDeviceToHost)) ;
-    return CHOLMOD_HIP_OK ;
 }
 
 int cholmod_hip_download_factor (cholmod_hip_plan *P, double *Lx_host)
@@ -1269,118 +950,6 @@ int cholmod_hip_factorize (cholmod_hip_plan *P, const int64_t *Sp, const int64_t
         if (rc2 != CHOLMOD_HIP_OK) return rc2 ;
     }
     return rc ;
-}
-
-static int ensure_check_tasks (cholmod_hip_plan *P) ;
-
-int cholmod_hip_factor_checks (cholmod_hip_plan *P, double *out5)
-{
-    if (!P || P->host_only || !out5) return CHOLMOD_HIP_INVALID ;
-    for (int q = 0 ; q < 5 ; q++) out5 [q] = 0 ;
-    if (P->nsuper == 0) return CHOLMOD_HIP_OK ;
-    HIP_TRY (ensure_check_tasks (P)) ;
-    HIPCHK (hipMemsetAsync (P->d_chk_out, 0, 5 * sizeof (double), P->stream)) ;
-    // (several ranks: the complete factor exists only after cholmod_hip_gather_factor)
-    if (!whole_factor (P) || !whole_fronts (P)) return CHOLMOD_HIP_INVALID ;
-    const bool cxs = (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;
-    CXS_LAUNCH (k_factor_checks, dim3 ((unsigned) P->nchk), dim3 (256), 0, P->stream,
-        P->d_chk, whole_fronts (P), whole_factor (P), P->d_chk_out) ;
-    HIPCHK (hipGetLastError ()) ;
-    HIPCHK (hipMemcpyAsync (out5, P->d_chk_out, 5 * sizeof (double), hipMemcpyDeviceToHost, P->stream)) ;
-    HIPCHK (hipStreamSynchronize (P->stream)) ;
-    return CHOLMOD_HIP_OK ;
-}
-
-/* Smallest and largest diagonal entry of the resident factor, and the number of NaN / negative ones: what
- * cholmod_l_rcond needs (reference CHOLMOD/Cholesky/cholmod_rcond.c:102-124 walks Lx [psx + jj + jj nsrow] on the host;
- * here L stays in HBM and three numbers come back).  Several ranks: after cholmod_hip_gather_factor. */
-int cholmod_hip_diag_minmax (cholmod_hip_plan *P, double *out3)
-{
-    if (!P || P->host_only || !out3) return CHOLMOD_HIP_INVALID ;
-    out3 [0] = out3 [1] = out3 [2] = 0 ;
-    if (P->n == 0) return CHOLMOD_HIP_OK ;
-    if (!whole_factor (P) || !whole_fronts (P)) return CHOLMOD_HIP_INVALID ;
-    HIP_TRY (ensure_check_tasks (P)) ;     // (d_chk_out: five doubles of scratch)
-    unsigned long long seed [3] ;
-    const double inf = INFINITY, zero = 0.0 ;
-    memcpy (&seed [0], &inf, 8) ; memcpy (&seed [1], &zero, 8) ; seed [2] = 0 ;
-    HIPCHK (hipMemcpyAsync (P->d_chk_out, seed, sizeof (seed), hipMemcpyHostToDevice, P->stream)) ;
-    const bool cxs = (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;
-    CXS_LAUNCH (k_diag_minmax, dim3 ((unsigned) ((P->n + 255) / 256)), dim3 (256), 0, P->stream,
-        P->n, P->d_supermap, whole_fronts (P), whole_factor (P), (unsigned long long *) P->d_chk_out) ;
-    HIPCHK (hipGetLastError ()) ;
-    HIPCHK (hipMemcpyAsync (seed, P->d_chk_out, sizeof (seed), hipMemcpyDeviceToHost, P->stream)) ;
-    HIPCHK (hipStreamSynchronize (P->stream)) ;
-    memcpy (&out3 [0], &seed [0], 8) ; memcpy (&out3 [1], &seed [1], 8) ; out3 [2] = (double) seed [2] ;
-    return CHOLMOD_HIP_OK ;
-}
-
-/* The same invariants over the fronts THIS rank answers for in a distributed factor (every front
- * belongs to the first rank of its group), read from the rank's own part of L -- no gathered copy
- * needed: the sums of out5 over all ranks are the invariants of the complete factor.  (One rank:
- * the same numbers as cholmod_hip_factor_checks.) */
-int cholmod_hip_factor_checks_local (cholmod_hip_plan *P, double *out5)
-{
-    if (!P || P->host_only || !out5) return CHOLMOD_HIP_INVALID ;
-    for (int q = 0 ; q < 5 ; q++) out5 [q] = 0 ;
-    if (P->nsuper == 0) return CHOLMOD_HIP_OK ;
-    if (!P->d_Lx) return CHOLMOD_HIP_INVALID ;          // (released by a host-staged gather: the gathered factor is what there is)
-    std::vector<CheckTask> t ;
-    for (i64 s = 0 ; s < P->nsuper ; s++)
-        if (P->lpx [s] >= 0 && (P->fr [s].own_w || P->rank == P->grp0 [s]))
-            for (int c0 = 0 ; c0 < P->fr [s].nscol ; c0 += CHK_COLS)
-                if (col_owned (P->fr [s], c0)) t.push_back (CheckTask {(i32) s, c0}) ;       // (a slab is a multiple of CHK_COLS columns)
-    if (t.empty ()) return CHOLMOD_HIP_OK ;
-    hipError_t e ;
-    CheckTask *dt = dupload (t, e) ; HIPCHK (e) ;
-    double *dout = nullptr ;
-    if (hipMalloc ((void **) &dout, 5 * sizeof (double)) != hipSuccess) { (void) hipGetLastError () ; (void) hipFree (dt) ; return CHOLMOD_HIP_OUT_OF_MEMORY ; }
-    (void) hipMemsetAsync (dout, 0, 5 * sizeof (double), P->stream) ;
-    const bool cxs = (P->flags & CHOLMOD_HIP_CX_STORAGE) != 0 ;
-    CXS_LAUNCH (k_factor_checks, dim3 ((unsigned) t.size ()), dim3 (256), 0, P->stream, dt, P->d_fr, P->d_Lx, dout) ;
-    e = hipGetLastError () ;
-    if (e == hipSuccess) e = hipMemcpyAsync (out5, dout, 5 * sizeof (double), hipMemcpyDeviceToHost, P->stream) ;
-    if (e == hipSuccess) e = hipStreamSynchronize (P->stream) ;
-    (void) hipFree (dt) ; (void) hipFree (dout) ;
-    return e == hipSuccess ? CHOLMOD_HIP_OK : CHOLMOD_HIP_GPU_PROBLEM ;
-}
-
-static int ensure_check_tasks (cholmod_hip_plan *P)
-{
-    if (P->d_chk) return CHOLMOD_HIP_OK ;
-    std::vector<CheckTask> t ;
-    for (i64 s = 0 ; s < P->nsuper ; s++)
-        for (int c0 = 0 ; c0 < P->fr [s].nscol ; c0 += CHK_COLS) t.push_back (CheckTask {(i32) s, c0}) ;
-    hipError_t e ;
-    P->d_chk = dupload (t, e) ; HIPCHK (e) ;
-    P->nchk = (i64) t.size () ;
-    HIPCHK (hipMalloc ((void **) &P->d_chk_out, 5 * sizeof (double))) ;
-    return CHOLMOD_HIP_OK ;
-}
-
-int cholmod_hip_download_even_columns (cholmod_hip_plan *P, double *out_host)
-{
-    if (!P || P->host_only || !out_host) return CHOLMOD_HIP_INVALID ;
-    if (P->nsuper == 0 || P->xsize == 0) return CHOLMOD_HIP_OK ;
-    if (P->flags & CHOLMOD_HIP_CX_STORAGE)
-    {
-        // the factor is stored as its even columns: it IS the interleaved complex factor
-        if (!whole_factor (P)) return CHOLMOD_HIP_INVALID ;
-        HIPCHK (hipMemcpy (out_host, whole_factor (P), (size_t) P->xsize * sizeof (double), hipMemcpyDeviceToHost)) ;
-        return CHOLMOD_HIP_OK ;
-    }
-    HIP_TRY (ensure_check_tasks (P)) ;
-    double *tmp = nullptr ;
-    const size_t bytes = (size_t) (P->xsize / 2) * sizeof (double) ;
-    if (hipMalloc ((void **) &tmp, bytes) != hipSuccess) { (void) hipGetLastError () ; return CHOLMOD_HIP_OUT_OF_MEMORY ; }
-    if (!whole_factor (P)) { (void) hipFree (tmp) ; return CHOLMOD_HIP_INVALID ; }
-    hipLaunchKernelGGL (k_even_columns, dim3 ((unsigned) P->nchk), dim3 (256), 0, P->stream,
-        P->d_chk, whole_fronts (P), whole_factor (P), tmp) ;
-    hipError_t e = hipGetLastError () ;
-    if (e == hipSuccess) e = hipMemcpyAsync (out_host, tmp, bytes, hipMemcpyDeviceToHost, P->stream) ;
-    if (e == hipSuccess) e = hipStreamSynchronize (P->stream) ;
-    (void) hipFree (tmp) ;
-    return e == hipSuccess ? CHOLMOD_HIP_OK : CHOLMOD_HIP_GPU_PROBLEM ;
 }
 
 int cholmod_hip_get_maps (cholmod_hip_plan *P, int64_t *sparent, int64_t *level, int64_t *relmap)

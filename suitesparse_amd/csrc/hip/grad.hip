@@ -105,7 +105,7 @@ template <typename T> static int upload (T **into, const std::vector<T> &v)
 }
 
 // The transposed product map and the scratch of vals_n doubles, built by the first gradient call after a
-// cholmod_hip_set_product_map (a caller who never differentiates pays nothing) and freed with the map (engine.hip:
+// cholmod_hip_set_product_map (a caller who never differentiates pays nothing) and freed with the map (values.hip:
 // drop_product_map).  The forward lists come down once (no kernel writes them); one stable counting pass on the host --
 // pairs in ascending p, the ia half of a pair before its ib half, so that the order of a list is a function of the map
 // alone --, a counting sort of the values into the kernel's three length classes (inside a class they keep their order),

@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(256) k_gr_panel (i64 n, i64 nz, const i64 *Sp,
     }
 }
 
-// ---- the chain rule through a product map: the transpose of k_product_values (kernels.hip.h) -------------------------------
+// ---- the chain rule through a product map: the transpose of k_product_values (values_kernels.hip.h) ------------------------
 //
 // vals [c] = sum over the pairs p of list c of a [ia [p]] a [ib [p]], and Gv [c] = d loss / d vals [c]; then
 //     g [q] = sum_{p : ia [p] = q} Gv [c (p)] a [ib [p]]  +  sum_{p : ib [p] = q} Gv [c (p)] a [ia [p]]

@@ -1,4 +1,6 @@
-// kernels.hip.h -- gfx950 device kernels of the supernodal Cholesky engine.
+// kernels.hip.h -- gfx950 device kernels of the supernodal Cholesky engine: what a factorization launches (engine.hip).
+// The kernels of the other device features have headers of their own, one per translation unit: the value upload
+// (values_kernels.hip.h), the checks on a finished factor (check_kernels.hip.h), the solves (solve_kernels.hip.h), ...
 //
 // The engine is a level-scheduled multifrontal formulation of the reference's
 // left-looking loop (CHOLMOD/Supernodal/t_cholmod_super_numeric.c:279-1048):
@@ -152,13 +154,6 @@ __global__ void __launch_bounds__(256) k_assemble_mapped (i64 nz, const i64 *ama
     if (q >= 0) Lx [q] = Sx [p] ;
 }
 
-// Sx [q] = values [src [q]]: new values of the caller's matrix into the resident S
-__global__ void __launch_bounds__(256) k_gather_values (i64 nz, const i64 *src, const double *values, double *Sx)
-{
-    i64 q = blockIdx.x * (i64) 256 + threadIdx.x ;
-    if (q < nz) Sx [q] = values [src [q]] ;
-}
-
 // One chunk of a value upload in batch order (round 6): staged entry k belongs to entry order [k] of S; it refreshes the
 // resident S (the thin-front kernels read their columns from there) and, where the entry has a place in L's generic
 // fronts, lands there.  "+=" into the cleared L: k_add_beta has run before, no two entries of S share a target.
@@ -172,37 +167,6 @@ __global__ void __launch_bounds__(256) k_values_chunk (i64 k0, i64 k1, const i64
     Sx [q] = v ;
     const i64 m = amap [q] ;
     if (m >= 0) Lx [m] += v ;
-}
-
-// Values that are not given but computed (cholmod_hip_set_product_map): vals [c] = sum over the pairs p of list c,
-// cp [c] <= p < cp [c + 1], of a [ia [p]] * a [ib [p]] -- the entries of tril (A A') from the values of A, a list per
-// entry, its pairs by ascending column of A.  Lists are 1 pair long (two rows of A that share one column) up to a whole
-// row of A (a diagonal entry of a dense row), so the entries come sorted into three classes by length (order [g]: the
-// entry group g of this launch owns) and a group of G lanes owns one entry:
-//     G = 1    lists of <= PM_LEN1 pairs: lane = entry, the lanes of a wave hold lists of about one length;
-//     G = 16   up to PM_LEN16: four entries to a wave, a list is at most PM_LEN16 / 16 rounds;
-//     G = 64   above: a wave walks one list 64 pairs a round, two independent gathers per lane in flight.
-// Lane l of a group adds the pairs l, l + G, l + 2 G, ... in that order (fused multiply-add), then the G partial sums
-// meet in a butterfly of fixed shape: one owner per entry, the order a function of the list alone, no floating-point
-// atomic -- the same values give the same bits, as in residual_kernels.hip.h.  Every index was checked on the host when
-// the map was set: nothing outside a [0 .. navalues) is read.  (PM_LEN1, PM_LEN16: descriptors.hip.h)
-template <int G>
-__global__ void __launch_bounds__(256) k_product_values (i64 ngroups, const i32 *order, const i64 *cp, const i64 *ia, const i64 *ib,
-    const double *a, double *vals)
-{
-    const i64 t = blockIdx.x * (i64) 256 + threadIdx.x ;
-    const i64 g = t / G ;
-    const int l = (int) (t % G) ;
-    // (a whole group leaves together: the shuffles below see the lanes of live groups only)
-    if (g >= ngroups) return ;
-    const i64 c = order [g] ;
-    const i64 p1 = cp [c + 1] ;
-    double acc = 0.0 ;
-#pragma unroll 2
-    for (i64 p = cp [c] + l ; p < p1 ; p += G) acc = __builtin_fma (a [ia [p]], a [ib [p]], acc) ;
-#pragma unroll
-    for (int w = G / 2 ; w > 0 ; w >>= 1) acc += __shfl_xor (acc, w, 64) ;
-    if (l == 0) vals [c] = acc ;
 }
 
 // Lx(k,k) += beta for the columns this rank's k_assemble owns (after k_assemble_mapped)
@@ -2468,44 +2432,6 @@ __global__ void __launch_bounds__(256) k_win_move (const WinD *g, int ng, double
     else if (mine) for (int i = ra + threadIdx.x ; i < rb ; i += (int) blockDim.x) sc [i] = wc [i] ;
 }
 
-// ---- extreme diagonal entries of L (cholmod_l_rcond on a device-resident factor) ---------------------
-// out [0] = min L_jj, out [1] = max L_jj (as ordered bit patterns of NON-NEGATIVE doubles: the caller seeds them with
-// +inf / 0), out [2] += number of NaN or negative diagonal entries; a diagonal entry -0.0 counts as +0.0 (a minimum of 0,
-// not a negative entry).  One thread per column; CX: a complex factor in its own
-// storage, the diagonal of the complex L is the (real) entry (2j, 2j) of the twin, kept in the even column 2j.
-template <bool CX>
-__global__ void __launch_bounds__(256) k_diag_minmax (i64 n, const i32 *supermap, const FrontD *fr, const double *Lx, unsigned long long *out)
-{
-    const i64 k = blockIdx.x * (i64) 256 + threadIdx.x ;
-    double v = 0 ;
-    bool have = false, bad = false ;
-    if (k < n && !(CX && (k & 1)))
-    {
-        const FrontD f = fr [supermap [k]] ;
-        const int jj = (int) (k - f.k1) ;
-        v = Lx [f.psx + jj + colx<CX> (jj, f.nsrow)] ;
-        have = true ;
-        if (!(v >= 0.0)) { bad = true ; have = false ; }        // (NaN or negative: counted, kept out of the extremes)
-        // a zero of either sign is the minimum +0.0: the bit pattern of -0.0 is above that of +inf as an unsigned integer,
-        // so it would win the wave's comparisons and then lose the atomicMin, and the wave's minimum with it
-        // (-0.0 + 0.0 = +0.0 in round-to-nearest, every other value unchanged; needs signed zeros, i.e. no fast-math build)
-        v = v + 0.0 ;
-    }
-    double lo = have ? v : __builtin_inf (), hi = have ? v : 0.0 ;
-    for (int o = 32 ; o > 0 ; o >>= 1)
-    {
-        const double l2 = __shfl_xor (lo, o), h2 = __shfl_xor (hi, o) ;
-        lo = l2 < lo ? l2 : lo ; hi = h2 > hi ? h2 : hi ;
-    }
-    const unsigned long long nbad = __popcll (__ballot (bad)) ;
-    if ((threadIdx.x & 63) == 0)
-    {
-        atomicMin (out, (unsigned long long) __double_as_longlong (lo)) ;
-        atomicMax (out + 1, (unsigned long long) __double_as_longlong (hi)) ;
-        if (nbad) atomicAdd (out + 2, nbad) ;
-    }
-}
-
 // ---- first failing supernode (not-positive-definite protocol) ---------------------
 // out [0] = smallest supernode with info != 0 (nsuper if none), so that the host reads
 // 4 bytes per factorization instead of the whole info array (G3_circuit stand-in:
@@ -2514,79 +2440,6 @@ __global__ void __launch_bounds__(256) k_first_fail (i64 nsuper, const i32 *info
 {
     i64 s = blockIdx.x * (i64) 256 + threadIdx.x ;
     if (s < nsuper && info [s] != 0) atomicMin (out, (int) s) ;
-}
-
-// ---- size-independent invariants of a device-resident factor ----------------
-// One pass over Lx (parity checks at sizes the CPU oracle cannot reach):
-//   out[0] += sum_j log L(j,j)          (= logdet(A)/2, analytic for Poisson grids)
-//   out[1] += entries != 0 in the dead strictly-upper triangles of the diagonal
-//             blocks (the reference never writes them);
-//             a NaN counts, -0.0 does not
-//   out[2] += non-finite entries of the lower trapezoids
-//   out[3] += sum of squares of the finite entries of the lower trapezoids (||L||_F^2)
-//   out[4] += diagonal entries that are not > 0 (zero of either sign, negative, NaN)
-// A workgroup owns CHK_COLS columns of one supernode; wave w takes the columns
-// == w (mod 4), lanes stride the rows (coalesced).
-// ---- even columns of the factor (complex input through the real embedding) ---------
-// The engine factors the 2n x 2n embedding of a complex matrix (host/complex.c); the
-// interleaved complex column j of a supernode is the even column 2j of the real one.
-// out (packed: supernode s at px [s] / 2, i.e. 2 * nsrow_c * nscol_c doubles) receives
-// them, the imaginary part of the diagonal as the exact zero zpotrf leaves.
-__global__ void __launch_bounds__(256) k_even_columns (const CheckTask *tasks, const FrontD *fr,
-    const double *Lx, double *out)
-{
-    const CheckTask T = tasks [blockIdx.x] ;
-    const FrontD &f = fr [T.front] ;
-    const int nsrow = f.nsrow, nscol = f.nscol ;
-    const double *L = Lx + f.psx ;
-    double *O = out + f.psx / 2 ;
-    const int c1 = T.c0 + CHK_COLS < nscol ? T.c0 + CHK_COLS : nscol ;
-    for (int c = T.c0 + (T.c0 & 1) ; c < c1 ; c += 2)
-        for (int i = threadIdx.x ; i < nsrow ; i += 256)
-            O [(i64) (c >> 1) * nsrow + i] = (i == c + 1) ? 0.0 : L [(i64) c * nsrow + i] ;
-}
-
-// (CX: the checks run on the twin the storage stands for -- ldx rebuilds the odd columns)
-template <bool CX>
-__global__ void __launch_bounds__(256) k_factor_checks (const CheckTask *tasks, const FrontD *fr,
-    const double *Lx, double *out)
-{
-    CheckTask T = tasks [blockIdx.x] ;
-    const FrontD &f = fr [T.front] ;
-    int nsrow = f.nsrow, nscol = f.nscol ;
-    int lane = threadIdx.x & 63, wave = threadIdx.x >> 6 ;
-    const double *L = Lx + f.psx ;
-    double slog = 0.0, sq = 0.0 ;
-    double nup = 0.0, nbad = 0.0, nneg = 0.0 ;
-    int c1 = T.c0 + CHK_COLS < nscol ? T.c0 + CHK_COLS : nscol ;
-    for (int j = T.c0 + wave ; j < c1 ; j += 4)
-    {
-        for (int i = lane ; i < nsrow ; i += 64)
-        {
-            double v = ldcx<CX> (L, i, col_local (f, j), nsrow) ;      // (a distributed front: the tasks cover this rank's slabs)
-            if (i < j) { if (v != 0.0) nup += 1.0 ; }
-            else
-            {
-                if (!(v - v == 0.0)) nbad += 1.0 ; else sq = __builtin_fma (v, v, sq) ;
-                if (i == j) { if (v > 0.0) slog += log (v) ; else nneg += 1.0 ; }
-            }
-        }
-    }
-    double acc [5] = {slog, nup, nbad, sq, nneg} ;
-    __shared__ double red [4][5] ;
-#pragma unroll
-    for (int q = 0 ; q < 5 ; q++)
-    {
-        double v = acc [q] ;
-        for (int o = 32 ; o > 0 ; o >>= 1) v += __shfl_down (v, o) ;
-        if (lane == 0) red [wave][q] = v ;
-    }
-    __syncthreads () ;
-    if (threadIdx.x < 5)
-    {
-        double v = (red [0][threadIdx.x] + red [1][threadIdx.x]) + (red [2][threadIdx.x] + red [3][threadIdx.x]) ;
-        if (v != 0.0) atomicAdd (&out [threadIdx.x], v) ;
-    }
 }
 
 } // namespace sship

@@ -1,9 +1,9 @@
 // plan.hip.h -- the types the host-side translation units of the engine share: the launch list (Launch, Schedule), the
 // contribution-block arena allocator, the RCCL entry points bound at run time, and the plan itself (cholmod_hip_plan:
 // one symbolic factor prepared for one rank).  plan_build.hip derives the plan (etree, ownership, layout, batches),
-// schedule_dense.hip the launches of a batch of fronts, engine.hip uploads and runs it, exchange.hip moves what its ranks
-// share, solve.hip solves with its factor, residual.hip forms residuals with its resident matrix, selinv.hip inverts on
-// the factor's pattern.
+// schedule_dense.hip the launches of a batch of fronts, engine.hip uploads and runs it, values.hip brings the matrix
+// values to it, checks.hip reads the finished factor, exchange.hip moves what its ranks share, solve.hip solves with its
+// factor, residual.hip forms residuals with its resident matrix, selinv.hip inverts on the factor's pattern.
 #pragma once
 #include "descriptors.hip.h"
 #include "../../../include/cholmod_hip.h"
@@ -107,7 +107,7 @@ struct Launch {
         hipGetErrorString (e_), __FILE__, __LINE__) ; return CHOLMOD_HIP_GPU_PROBLEM ; } } while (0)
 // a step that returns a status: the first failure is the caller's result
 #define HIP_TRY(call) do { int rc_ = (call) ; if (rc_ != CHOLMOD_HIP_OK) return rc_ ; } while (0)
-// (solves, checks) K<true> for a complex factor in its own storage; needs `cxs` in scope
+// (factorization, solves, checks) K<true> for a complex factor in its own storage; needs `cxs` in scope
 #define CXS_LAUNCH(K, ...) do { if (cxs) hipLaunchKernelGGL (K<true>, __VA_ARGS__) ; else hipLaunchKernelGGL (K<false>, __VA_ARGS__) ; } while (0)
 
 // best-fit free-list allocator for the contribution-block arena (plan time)

@@ -655,7 +655,7 @@ struct PlanBuilder
             // (round 6) a class of very many fronts -- the leaves of a 2D / circuit problem: 65 136 in one launch at the
             // G3_circuit stand-in -- goes out as four launches over consecutive fronts: run from a resident S they cost
             // three launch latencies; fed by cholmod_l_factorize from host memory, each waits for its own quarter of the
-            // values only (the upload travels in the order of the launches, engine.hip: cholmod_hip_set_value_map)
+            // values only (the upload travels in the order of the launches, values.hip: cholmod_hip_set_value_map)
             const size_t nb_ = bucket [c].size () ;
             const int parts = (P->world == 1 && nb_ >= 16384) ? 4 : 1 ;
             for (int part = 0 ; part < parts ; part++)

@@ -1,4 +1,4 @@
-"""The values-only path of cholmod_l_factorize (host/numeric.c: factorize_values_only, engine.hip: cholmod_hip_values_begin /
+"""The values-only path of cholmod_l_factorize (host/numeric.c: factorize_values_only, values.hip: cholmod_hip_values_begin /
 _push_chunk) under every team shape of its roles table, in batch order and in S order, and the state of L when the long way
 after a hash mismatch fails.  The sequence of calls is test_factorize_again_with_new_values_and_with_a_new_pattern's; run
 as a script this module is the child process of the tests below:
